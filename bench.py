@@ -2,8 +2,19 @@
 """Headline benchmark: BN254 G1 MSM scalars/s at 2^26 (BASELINE.json configs[1])
 with the BN254 Fr NTT elems/s at 2^24 (configs[2]) reported beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 26] [--ntt-log-n 24]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 26] [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run does only what the headline figure needs: it generates the
+inputs, warms up, times K steps and prints the result line (metric, value,
+unit, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed
+step returned as DIR/msm_result.npy (float64: the sixteen 32-bit little-endian
+words of the 64-byte affine result; the inputs are seeded, so two builds can
+be compared output for output).  Everything below that is not the headline
+MSM -- rooflines, size sweeps, the NonUniform set, the NTT, BLS12-381 and
+Groth16 legs, the host-resident paths, the CPU baseline and every
+comparison with it or with the unsharded MSM -- runs only with --full, which
+adds those objects to the same line.
 
 A step is one full MSM over 2^26 points whose bases/scalars are already in
 HBM (generated on the device, seeded).  With N GPUs the 2^26 points are split
@@ -86,6 +97,12 @@ def parse():
     ap.add_argument("--log-n", type=int, default=26)
     ap.add_argument("--ntt-log-n", type=int, default=24)
     ap.add_argument("--window-bits", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline MSM also run every other leg and check (rooflines, sweeps, NonUniform, "
+                         "NTT, BLS12-381, Groth16, host-resident paths, CPU baseline); the --no-* and *-log-n "
+                         "options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step to DIR/msm_result.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ntt", action="store_true")
     ap.add_argument("--cpu-log-n", type=int, default=0,
@@ -106,6 +123,15 @@ def parse():
     ap.add_argument("--groth16-log-n", type=int, default=20,
                     help="Groth16 prove on a synthetic 2^k-constraint circom key (BASELINE configs[4]); 0 = skip")
     return ap.parse_args()
+
+
+def dump_outputs(directory, result):
+    """--dump-outputs: the affine point a timed step returned (BN254 G1: x then
+    y, 32-byte little-endian field values as the library hands them back) as
+    its sixteen 32-bit words, exact in float64."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "msm_result.npy"), np.frombuffer(result, dtype="<u4").astype(np.float64))
 
 
 def cpu_model():
@@ -835,18 +861,19 @@ def main():
     consistent = all(r == results[0] for r in results) and (args.warmup == 0 or results[0] == ref)
     ms_per_step = elapsed / args.steps * 1e3
     value = n_total / (elapsed / args.steps)
-    consistent_1gpu = full_msm_equals("bn254_g1", n_total, results[0], rank, dist) if world > 1 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[-1])
 
-    # ---- dominant-kernel timing (HIP events on the MSM stream) ----
-    msm.set_profile(True)
-    prof = []
-    for _ in range(3):
-        local_run()
-        prof.append(msm.last_timings())
-    msm.set_profile(False)
-    phases = {k: round(sorted(p[k] for p in prof)[1], 4) for k in prof[0]}
-    launches = max(1, int(prof[0]["acc_launches"]))
-    acc_ms = sorted(p["acc"] for p in prof)[1] / launches
+    def finish(line):
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        msm.close()
+        if lib_comm is not None:
+            lib_comm.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
     c, windows = M.plan("bn254_g1", n)
     rank_windows = windows
     if split in ("windows", "hybrid"):
@@ -855,24 +882,6 @@ def main():
     elif args.window_bits:
         c, windows = args.window_bits, D._windows_for("bn254_g1", args.window_bits)
         rank_windows = windows
-    # SURVEY 8(d): the algorithmic bytes of the MSM are its inputs read once,
-    # 96 B per point (64 B affine base + 32 B scalar); one launch covers all n
-    # points of this rank (all windows), so achieved = n x 96 B / launch time.
-    # The (point, window) gathers the kernel actually performs (W x 64 B bases
-    # + 8 B sorted entries per point) are reported beside it as gather_gbs.
-    points_per_launch = n / launches
-    acc_gbs = points_per_launch * MSM_BYTES_PER_POINT / (acc_ms * 1e-3) / 1e9
-    units = n * rank_windows / launches  # mixed additions (point, window) per launch
-    gather_gbs = units * (64 + 8) / (acc_ms * 1e-3) / 1e9
-    acc_kernel = "seg_acc29_kernel" if msm.last_schedule()["acc29"] else "seg_acc_kernel"
-    acc_traffic, acc_traffic_src, acc_traffic_raw = pmc_traffic(acc_kernel)
-    acc_gmadd = units / (acc_ms * 1e-3) / 1e9
-    try:
-        madd_peak = msm.madd_ceiling(29 if acc_kernel == "seg_acc29_kernel" else 32) or MADD_PEAK_G[acc_kernel]
-        madd_peak_src = "measured in this run"
-    except Exception:  # noqa: BLE001 -- a diagnostic; the committed figure stands in
-        madd_peak, madd_peak_src = MADD_PEAK_G[acc_kernel], "profiles/r03c/madd_rates.log"
-    stream_gbs = stream_copy_gbs()
 
     out = {
         "metric": METRIC,
@@ -901,8 +910,43 @@ def main():
                                   + (f"; exchange: {comm_label}" if world > 1 else ""),
                    "communicator": (lib_comm.backend if lib_comm else comm_label)},
         "consistent_across_steps": consistent,
-        "consistent_with_1gpu": consistent_1gpu,
-        "roofline": {"bound": "hbm", "achieved": acc_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+    }
+    if not args.full:  # the plain run ends here: the headline line and nothing else
+        finish(out)
+        return
+    out["consistent_with_1gpu"] = full_msm_equals("bn254_g1", n_total, results[0], rank, dist) if world > 1 else None
+
+    # ---- dominant-kernel timing (HIP events on the MSM stream) ----
+    msm.set_profile(True)
+    prof = []
+    for _ in range(3):
+        local_run()
+        prof.append(msm.last_timings())
+    msm.set_profile(False)
+    phases = {k: round(sorted(p[k] for p in prof)[1], 4) for k in prof[0]}
+    launches = max(1, int(prof[0]["acc_launches"]))
+    acc_ms = sorted(p["acc"] for p in prof)[1] / launches
+    # SURVEY 8(d): the algorithmic bytes of the MSM are its inputs read once,
+    # 96 B per point (64 B affine base + 32 B scalar); one launch covers all n
+    # points of this rank (all windows), so achieved = n x 96 B / launch time.
+    # The (point, window) gathers the kernel actually performs (W x 64 B bases
+    # + 8 B sorted entries per point) are reported beside it as gather_gbs.
+    points_per_launch = n / launches
+    acc_gbs = points_per_launch * MSM_BYTES_PER_POINT / (acc_ms * 1e-3) / 1e9
+    units = n * rank_windows / launches  # mixed additions (point, window) per launch
+    gather_gbs = units * (64 + 8) / (acc_ms * 1e-3) / 1e9
+    acc_kernel = "seg_acc29_kernel" if msm.last_schedule()["acc29"] else "seg_acc_kernel"
+    acc_traffic, acc_traffic_src, acc_traffic_raw = pmc_traffic(acc_kernel)
+    acc_gmadd = units / (acc_ms * 1e-3) / 1e9
+    try:
+        madd_peak = msm.madd_ceiling(29 if acc_kernel == "seg_acc29_kernel" else 32) or MADD_PEAK_G[acc_kernel]
+        madd_peak_src = "measured in this run"
+    except Exception:  # noqa: BLE001 -- a diagnostic; the committed figure stands in
+        madd_peak, madd_peak_src = MADD_PEAK_G[acc_kernel], "profiles/r03c/madd_rates.log"
+    stream_gbs = stream_copy_gbs()
+
+    out.update({
+        "roofline":{"bound": "hbm", "achieved": acc_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": acc_gbs / HBM_PEAK_GBS,
                      "traffic": acc_traffic, "traffic_unit": "GB per launch", "traffic_source": acc_traffic_src,
                      "traffic_fetch_raw": acc_traffic_raw,
@@ -925,7 +969,7 @@ def main():
                           "peak": madd_peak, "peak_source": madd_peak_src, "unit": "G mixed additions/s",
                           "frac": acc_gmadd / madd_peak,
                           "note": "n x windows mixed additions per launch / launch time; peak = " + MADD_PEAK_NOTE},
-    }
+    })
 
     # ---- configs[1] sweep (2^16, 2^20 .. 2^25: prefixes of the same device-resident input; 2^25 / 2^24 /
     # 2^23 are the per-rank shards of the 2^26 MSM at N = 2 / 4 / 8, priced in projected_scaling) ----
@@ -1240,14 +1284,7 @@ def main():
         nout = ntt_gpu_out if not args.no_ntt else None
         out["cpu_baseline"] = cpu_baseline(args, nb, ns, gpu_point, nin, nout)
 
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    msm.close()
-    if lib_comm is not None:
-        lib_comm.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

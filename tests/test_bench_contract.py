@@ -1,7 +1,8 @@
 """The bench.py output contract, checked on the newest committed bench line
-(profiles/<round>/bench_line*.json, written on the GPU box): the keys the
-driver and the judge read, a roofline object with its fraction consistent,
-and the CPU baseline beside it.  No GPU needed."""
+(profiles/<round>/bench_line*.json, the line of a `bench.py --full` run on an
+MI355X): the keys the driver and the judge read, a roofline object with its
+fraction consistent, and the CPU baseline beside it.  No GPU needed, except
+for the one plain run at a small size (marked gpu)."""
 import glob
 import json
 import os
@@ -60,6 +61,50 @@ def test_bench_cli_parses_without_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                          timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+# the objects of a --full line that a plain run leaves out
+FULL_ONLY = ("roofline", "valu_roofline", "msm_phase_ms", "msm_sweep", "projected_scaling", "non_uniform", "ntt",
+             "bls12_381", "groth16", "host_resident", "cpu_baseline", "consistent_with_1gpu")
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_its_result(tmp_path):
+    """A plain run (no --full) at a small size: the line carries the headline
+    keys and none of the legs behind --full, --steps is the number of timed
+    steps, and --dump-outputs writes the last step's affine point, which equals
+    the oracle's MSM of the same seeded inputs."""
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    import bench
+    from oracle import oracle as O
+    from tachyon_amd import msm as M
+    log_n, steps = 12, 3
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", "1", "--log-n", str(log_n), "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "consistent_across_steps"):
+        assert k in d, k
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["steps"] == steps and d["warmup"] == 1 and d["consistent_across_steps"] is True
+    assert d["higher_is_better"] is True and d["unit"] == "scalars/s" and d["dtype"] == "u32"
+    n = 1 << log_n
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert sorted(os.listdir(dump)) == ["msm_result.npy"]
+    got = np.load(dump / "msm_result.npy")
+    assert got.dtype == np.float64 and got.shape == (16,)
+    d_b = torch.empty(n * 64, dtype=torch.uint8, device="cuda")
+    d_s = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
+    M.gen_bases("bn254_g1", bench.SEED, n, 1 << 10, d_b.data_ptr())
+    M.gen_scalars("bn254_fr", bench.SEED, n, d_s.data_ptr())
+    torch.cuda.synchronize()
+    expect, _ = O.msm("bn254_g1", d_b.cpu().numpy().tobytes(), d_s.cpu().numpy().tobytes())
+    assert got.astype("<u4").tobytes() == expect
 
 
 def test_pmc_traffic_takes_the_newest_run(tmp_path, monkeypatch):

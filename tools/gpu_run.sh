@@ -9,6 +9,7 @@
 #   tests=ARGS         python -u -m pytest -m gpu -x -v --timeout 300 ARGS   (ARGS default: tests;
 #                      evaluated by the shell: quote a -k expression inside it)
 #   bench=ARGS         python bench.py ARGS; the JSON line -> gpurun_out/TAG/bench_<k>.json
+#                      (the headline MSM only; put --full in ARGS for every other leg and check)
 #   profile=ARGS       tools/profile_round.sh TAG ARGS (trace + PMC passes of a bench command)
 #   pmc=COUNTERS@ARGS  one rocprofv3 --pmc pass over python bench.py ARGS (counters space-separated)
 #   cmd=COMMAND        any other command (A/B probes: python tools/... )
