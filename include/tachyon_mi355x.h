@@ -603,6 +603,34 @@ TACHYON_C_EXPORT void tachyon_mi355x_field_op(int field, int op, const void* a, 
 /* point op: 0 add (affine + affine), 1 double, 2 add-mixed into xyzz of a. Affine in/out. */
 TACHYON_C_EXPORT void tachyon_mi355x_ec_op(int curve, int op, const void* a, const void* b, void* out, size_t count);
 
+/* Elementwise device parity kernels of the carry-free limb fields of the hot
+ * kernels, on RAW limbs (no conversion in or out: the caller sets every limb).
+ * family: 0 f29 (BN254 Fq, N = 9 limbs of 29 bits, 8 words), 1 f28 (BLS12-381
+ * Fq, N = 14 limbs of 28 bits, 12 words), 2 fr29 (BN254 Fr, N = 9).  `in` holds
+ * `count` elements of in_words and `out` of out_words 32-bit words each
+ * (tachyon_mi355x_limb_op_words; 0 for an unknown op), operands in the order
+ * given, N limbs each.  Families 0 and 1, one lane per element:
+ *   0 mul(a,b) 1 mul_add(a,b,e) 2 mul2_add(a,b,c,d) 3 mul2_add(a,b,c,d,e)
+ *   4 sqr(a) 5 sqr_add(a,e) 6 normalize(a) 7 from32(words) 8 to32(a) -> words
+ *   9 is_zero_mod_p(a) -> 1 word  10 reduce_shl5 / reduce(a)
+ *   11 from_shifted(x2,y2) 12 madd(acc,x2,y2) 13 add(acc,acc) 14 dbl(acc) of
+ *   acc29_core / acc28_core: acc = X, Y, ZZ, ZZZ; out = acc and `special`.
+ * Families 0 and 1, a lane pair per element (pair29 / pair28; every Fq2 value
+ * is its c0 limbs then its c1 limbs, lane h works on component h):
+ *   20 pzero(a) -> 2 words  21 from_shifted(x2,y2) 22 madd(acc,x2,y2)
+ *   23 add(acc,acc) 24 dbl(acc): out = acc (4 Fq2 values), then both lanes'
+ *   `special`.
+ *   32 + 8 kind + k: kind 0 pmul<K>(a,b) 1 pmul_add<K>(a,b,e) 2 psqr<K>(a)
+ *   3 psqr_add<K>(a,e); k: 0 kK4 1 kK8 2 kK16 3 kK32 4 kK32r3 5 kK8r1 -- only
+ *   the pairs (kind, K) the point formulas instantiate.
+ * Family 2: 0 mont(a,b) 1 shoup(a,w,wq) 2 reduce(a) 3 from_words(8 words)
+ *   4 to_canonical_words(a) -> 8 words  5 radix4(x[4], 4 Shoup twiddles w,wq)
+ *   6 radix4(x[4], 4 R'-form twiddles) 7 radix4_last(x[4], w,wq)
+ *   8 radix2(x[2], w,wq) 9 radix2_last(x[2]).
+ * Host buffers in and out. */
+TACHYON_C_EXPORT void tachyon_mi355x_limb_op(int family, int op, const uint32_t* in, uint32_t* out, size_t count);
+TACHYON_C_EXPORT int tachyon_mi355x_limb_op_words(int family, int op, int* in_words, int* out_words);
+
 /* Groth16 prover over a circom zkey (no reference C-ABI --
  * the reference drives this path from C++: vendors/circom/prover_main.cc:82-160,
  * QuadraticArithmeticProgram::WitnessMapFromMatrices

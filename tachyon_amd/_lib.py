@@ -155,6 +155,8 @@ SIGNATURES = [
     ("tachyon_mi355x_gen_bases_at", None, [i32, u64, sz, sz, sz, vp, vp]),
     ("tachyon_mi355x_field_op", None, [i32, i32, vp, vp, vp, sz]),
     ("tachyon_mi355x_ec_op", None, [i32, i32, vp, vp, vp, sz]),
+    ("tachyon_mi355x_limb_op", None, [i32, i32, vp, vp, sz]),
+    ("tachyon_mi355x_limb_op_words", i32, [i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("tachyon_mi355x_groth16_prover_create", vp, [vp, sz]),
     ("tachyon_mi355x_groth16_prover_destroy", None, [vp]),
     ("tachyon_mi355x_groth16_prover_info", None, [vp, ctypes.POINTER(ctypes.c_uint32)]),

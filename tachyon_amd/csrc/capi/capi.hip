@@ -668,6 +668,12 @@ void tachyon_mi355x_field_op(int field, int op, const void* a, const void* b, vo
 void tachyon_mi355x_ec_op(int curve, int op, const void* a, const void* b, void* out, size_t count) {
   GUARD_BEGIN util::ec_op(curve, op, a, b, out, count); GUARD_END
 }
+void tachyon_mi355x_limb_op(int family, int op, const uint32_t* in, uint32_t* out, size_t count) {
+  GUARD_BEGIN util::limb_op(family, op, in, out, count); GUARD_END
+}
+int tachyon_mi355x_limb_op_words(int family, int op, int* in_words, int* out_words) {
+  return util::limb_op_words(family, op, in_words, out_words) ? 1 : 0;
+}
 
 void tachyon_mi355x_jacobian_destroy(int curve, void* jac) {
   switch (curve) {

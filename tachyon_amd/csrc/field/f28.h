@@ -179,7 +179,8 @@ TA_HD F28 shl8_repack(const uint32_t* w) {
 
 // value - q p, q = floor(v / p) - 0..2 from the top two limbs in float
 // (v_hi = l13 2^28 + l12, p_hi = p >> 336 ~ 2^44.7): N-form, < 3p, for
-// N-form inputs below 2^400.  Signed carries (v_mad_i64_i32 chains).
+// any N-form input (a 32-bit top limb: values below 2^396).  Signed carries
+// (v_mad_i64_i32 chains).
 TA_HD F28 reduce(const F28& v) {
   const float vf = (float)v.l[kN - 1] * 268435456.0f + (float)v.l[kN - 2];
   int q = (int)(vf * kInvPhi) - 1;

@@ -46,6 +46,10 @@ constexpr uint32_t kK4[9] = {0x21f3f51cu, 0x241182dau, 0x31ca8d3bu, 0x2b548b42u,
 // 8p, low limbs raised by 2^31 (>= 2^31 - 4)
 constexpr uint32_t kK8[9] = {0x83e7ea38u, 0x882305b2u, 0x83951a74u, 0x96a91683u, 0x8c2ecbbcu,
                              0x96da0601u, 0x85370a04u, 0x92e1319cu, 0x0183226fu};
+// 8p, low limbs raised by 2^29 (minus a normalized value < 8p where kK8's wide limbs
+// would overflow a column: the lane-pair square of msm/pair29.h add)
+constexpr uint32_t kK8r1[9] = {0x23e7ea38u, 0x282305b5u, 0x23951a77u, 0x36a91686u, 0x2c2ecbbfu,
+                               0x36da0604u, 0x25370a07u, 0x32e1319fu, 0x01832272u};
 // 16p, low limbs raised by 2^29
 constexpr uint32_t kK16[9] = {0x27cfd470u, 0x30460b6bu, 0x272a34efu, 0x2d522d0du, 0x385d9780u,
                               0x2db40c09u, 0x2a6e1410u, 0x25c2633fu, 0x030644e6u};
@@ -237,8 +241,10 @@ TA_HD void repack32(const F29& x, uint32_t* w) {
 // R-form words (x~ < 2^255) -> R' form x' = x~ 2^5 - q p, value < 3p: no
 // product, the quotient estimated from the top two limbs.  With v = x~ << 5
 // and v_hi = v >> 203, v_hi / (p_hi + 1) <= v / p < v_hi / (p_hi + 1) + 2^-40,
-// so the float estimate (relative error < 2^-21, times q < 64) minus one is
-// q* - 2 .. q*, q* = floor(v / p): 0 <= v - q p < 3p.
+// so the float estimate (relative error < 2^-21, times q < 85) minus one is
+// q* - 2 .. q*, q* = floor(v / p): 0 <= v - q p < 3p.  (The device fuses
+// l8 2^29 + l7 into one multiply-add; the product is exact, so host and device
+// agree.  tests/test_gpu_limb_fields.py runs it at every quotient boundary.)
 constexpr float kInvPhi = 1.0f / 1702635872462389.0f;  // 1 / (p >> 203 + 1)
 TA_HD F29 reduce_shl5(const F29& v) {
   const float vf = (float)v.l[8] * 536870912.0f + (float)v.l[7];

@@ -2,7 +2,8 @@
 // accumulation's mixed addition and the reductions' addition and doubling,
 // with the value bounds they rely on.  Host and device (the host build runs
 // f29.h's C++ columns; tests/test_f29_host.py checks these formulas against
-// Python integers with operands at the top of their bounds).
+// Python integers with operands at the top of their bounds, and
+// tests/test_gpu_limb_fields.py the device build on the same operands).
 #pragma once
 #include "../field/f29.h"
 

@@ -16,7 +16,8 @@
 //   Y3  = R T + (4p - W)  < 5.2   (T negated as 32p - T, limbs < 3 2^28)
 //   ZZ3 = ZZ PP, ZZZ3 = ZZZ PPP < 1.01
 // tests/test_pair28_model.py runs these formulas on the exact limb model with
-// operands at the top of their bounds (values, limbs, 64-bit columns).
+// operands at the top of their bounds (values, limbs, 64-bit columns);
+// tests/test_gpu_limb_fields.py runs this code on the same operands.
 #pragma once
 #include "../field/f28.h"
 #include "acc_pair.h"

@@ -20,7 +20,8 @@
 //   Y3  = R T + (4p - W)  < 5.9   (T negated as 32p - T, limbs < 3 2^29)
 //   ZZ3 = ZZ PP, ZZZ3 = ZZZ PPP < 1.09
 // tests/test_pair29_model.py runs these formulas on the exact limb model with
-// operands at the top of their bounds (values, 32-bit limbs, 64-bit columns).
+// operands at the top of their bounds (values, 32-bit limbs, 64-bit columns);
+// tests/test_gpu_limb_fields.py runs this code on the same operands.
 #pragma once
 #include "../field/f29.h"
 #include "acc_pair.h"
@@ -150,7 +151,11 @@ __device__ __forceinline__ Acc dbl(const Acc& A, bool h) {
 // add-2008-s (point_xyzz_impl.h:45-97) for the G2 reductions, both operands
 // not the identity (the caller keeps identity flags); inputs and outputs
 // X < 10p, Y < 6p, ZZ, ZZZ < 3p (from32 loads give < 3p), R reduced before its
-// square, P squared as it is with the 8p negation constant; *special as madd's
+// square, P (< 5.4p) squared as it is with an 8p negation constant -- kK8r1,
+// limbs < 1.5 2^30: lane 0's (P0 + P1)(P0 + 8p - P1) has 8 products of up to
+// 2^30 x (2^29 + K) in column 7, which with kK8's limbs (> 2^31, sized for
+// PPP + 2Q) passes 2^64 when both components' low limbs are near 2^29
+// (tests/limb_model.py asserts every column); *special as madd's
 // (tests/test_pair29_model.py point_add)
 __device__ __forceinline__ Acc add(const Acc& A, const Acc& B, bool h, int* special) {
   // ZZ1 ZZ2 and ZZZ1 ZZZ2 first: the operands' Z coordinates die early (register pressure)
@@ -162,7 +167,7 @@ __device__ __forceinline__ Acc add(const Acc& A, const Acc& B, bool h, int* spec
     *special = pzero(R) ? 2 : 1;
     return A;
   }
-  const F29 PP = psqr<kK8>(P, h);
+  const F29 PP = psqr<kK8r1>(P, h);
   const F29 PPP = pmul<kK4>(P, PP, h);
   const F29 Q = pmul<kK4>(U1, PP, h);
   const F29 W = pmul<kK4>(S1, PPP, h);

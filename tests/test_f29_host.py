@@ -5,8 +5,9 @@ the madd bound analysis relies on -- and the point formulas built on it
 (msm/acc29.h: the accumulation's madd, the reductions' add and dbl, the run
 start) on operands at the top of their bounds.  The device
 products (field/f29_asm.h) are the generator's output of the same columns;
-they are pinned here against tools/gen_f29_asm.py and on the GPU by the MSM
-golden tests (tests/test_gpu_msm.py, variant 8192)."""
+they are pinned here against tools/gen_f29_asm.py as text, and run on the GPU
+at these operand bounds, limb for limb against the shared model
+(tests/limb_model.py), by tests/test_gpu_limb_fields.py."""
 import importlib.util
 import os
 import random
@@ -14,10 +15,13 @@ import subprocess
 
 import pytest
 
+from limb_model import F29, point_cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
 R1 = pow(2, 261, P)  # R' = 2^261
 M29 = (1 << 29) - 1
+assert (F29.P, F29.R1, F29.M) == (P, R1 % P, M29)
 
 HARNESS = r"""
 #include <cstdio>
@@ -35,6 +39,8 @@ int main() {
     else if (!strcmp(op, "mul")) { rd(a); rd(b); wr(mul(a, b)); }
     else if (!strcmp(op, "mul_add")) { rd(a); rd(b); rd(c); wr(mul_add(a, b, c)); }
     else if (!strcmp(op, "mul2_add")) { rd(a); rd(b); rd(c); rd(d); wr(mul2_add(a, b, c, d)); }
+    else if (!strcmp(op, "mul2_add5")) { F29 e; rd(a); rd(b); rd(c); rd(d); rd(e); wr(redc<true, true>(a, b, c, d, e)); }
+    else if (!strcmp(op, "reduce")) { rd(a); wr(reduce_shl5(a)); }
     else if (!strcmp(op, "sqr")) { rd(a); wr(sqr(a)); }
     else if (!strcmp(op, "sqr_add")) { rd(a); rd(b); wr(sqr_add(a, b)); }
     else if (!strcmp(op, "iszero")) { rd(a); printf("%d\n", (int)is_zero_mod_p(a)); }
@@ -59,21 +65,7 @@ def harness(tmp_path_factory):
     return run
 
 
-def limbs(v):
-    """N-form limbs of v (limbs 0..7 exact, limb 8 the rest)."""
-    return [(v >> (29 * i)) & M29 for i in range(8)] + [v >> 232]
-
-
-def value(ls):
-    return sum(x << (29 * i) for i, x in enumerate(ls))
-
-
-def words(v):
-    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
-
-
-def n_form(ls):
-    return all(x <= M29 for x in ls[:8]) and ls[8] < (1 << 32)
+limbs, value, words, n_form = F29.limbs, F29.value, F29.words, F29.n_form
 
 
 def fmt(op, *xs):
@@ -126,6 +118,8 @@ def test_products(harness):
 def test_is_zero(harness):
     rng = random.Random(3)
     xs = [k * P for k in range(64)] + [k * P + 1 for k in range(64)] + [rng.randrange(64 * P) for _ in range(100)]
+    # k p + j 2^32 passes the one-multiply filter (the low word is k p's) and must fail the full compare
+    xs += [k * P + (j << 32) for k in range(64) for j in (1, 2, rng.randrange(1, 1 << 200))]
     out = harness([fmt("iszero", limbs(x)) for x in xs])
     for x, r in zip(xs, out):
         assert r[0] == int(x % P == 0)
@@ -186,71 +180,6 @@ def point_harness(tmp_path_factory):
     return run
 
 
-def _affine_add(P, Q):
-    if P is None:
-        return Q
-    if Q is None:
-        return P
-    (x1, y1), (x2, y2) = P, Q
-    if x1 == x2:
-        if (y1 + y2) % P_MOD == 0:
-            return None
-        lam = 3 * x1 * x1 * pow(2 * y1, -1, P_MOD) % P_MOD
-    else:
-        lam = (y2 - y1) * pow(x2 - x1, -1, P_MOD) % P_MOD
-    x3 = (lam * lam - x1 - x2) % P_MOD
-    return x3, (lam * (x1 - x3) - y1) % P_MOD
-
-
-P_MOD = P
-
-
-def _mul(k, Pt):
-    R = None
-    while k:
-        if k & 1:
-            R = _affine_add(R, Pt)
-        Pt = _affine_add(Pt, Pt)
-        k >>= 1
-    return R
-
-
-def _top_rep(v, bound):
-    """The representative v + k p below bound * p with the largest low limbs
-    (the widest columns), as N-form limbs."""
-    best = None
-    for k in range(bound):
-        w = v + k * P
-        if w >= bound * P:
-            break
-        s = sum(limbs(w)[:8])
-        if best is None or s > best[0]:
-            best = (s, w)
-    return limbs(best[1])
-
-
-def _acc(pt, z, bx=10, by=3, bz=3):
-    """XYZZ accumulator of affine pt with Z = z, R' form, representatives at the
-    top of the invariant X < bx p, Y < by p, ZZ, ZZZ < bz p."""
-    x, y = pt
-    zz, zzz = z * z % P, z * z * z % P
-    m = lambda v: v * R1 % P  # noqa: E731
-    return (_top_rep(m(x * zz % P), bx) + _top_rep(m(y * zzz % P), by) + _top_rep(m(zz), bz)
-            + _top_rep(m(zzz), bz))
-
-
-def _point_of(res):
-    """(special, affine point or None, component values) of a harness result."""
-    sp, v = res[0], res[1:]
-    X, Y, ZZ, ZZZ = (value(v[9 * i:9 * i + 9]) for i in range(4))
-    inv = pow(R1, -1, P)
-    if ZZ % P == 0:
-        return sp, None, (X, Y, ZZ, ZZZ), v
-    x = X * inv * pow(ZZ * inv, -1, P) % P
-    y = Y * inv * pow(ZZZ * inv, -1, P) % P
-    return sp, (x, y), (X, Y, ZZ, ZZZ), v
-
-
 def _check_bounds(vals, v, bx, by, bz):
     X, Y, ZZ, ZZZ = vals
     assert X < bx * P and Y < by * P and ZZ < bz * P and ZZZ < bz * P
@@ -265,51 +194,12 @@ def test_point_formulas_at_bounds(point_harness):
     10p, Y, ZZ, ZZZ < 3p), N-form limbs, and the special cases (P = acc ->
     doubling, P = -acc -> identity)."""
     rng = random.Random(7)
-    G = (1, 2)
-    pts = [_mul(rng.randrange(1, 1 << 64), G) for _ in range(24)]
-    lines, want = [], []
-    for i in range(0, 24, 2):
-        A, B = pts[i], pts[i + 1]
-        za, zb = rng.randrange(1, P), rng.randrange(1, P)
-        acc_a, acc_b = _acc(A, za), _acc(B, zb)
-        # base B for madd: R-form x~ = x 2^256 mod p (canonical), shifted by 5
-        xt, yt = B[0] * 2**256 % P, B[1] * 2**256 % P
-        lines.append(" ".join(map(str, ["madd"] + acc_a + limbs(xt << 5) + limbs(yt << 5))))
-        want.append(("madd", _affine_add(A, B), 0))
-        # the negated base (the kernel's p - y~ for a negative digit)
-        lines.append(" ".join(map(str, ["madd"] + acc_a + limbs(xt << 5) + limbs((P - yt) << 5))))
-        want.append(("madd", _affine_add(A, (B[0], P - B[1])), 0))
-        xa, ya = A[0] * 2**256 % P, A[1] * 2**256 % P
-        # the kernel's negation in 29-bit limbs (msm_impl.h Pol29::repack_y): 33p - y~ << 5 with
-        # kK33's raised limbs, at the top of its bound (y~ = 0 gives 33p itself)
-        k33 = [0x281ca627, 0x2190778e, 0x2ac70d2f, 0x3d797cec, 0x26410879, 0x3e4358d5, 0x35830962,
-               0x39e0ecb3, 0x063cee1b]
-        assert value(k33) == 33 * P
-        lines.append(" ".join(map(str, ["madd"] + acc_a + limbs(xt << 5) +
-                                  [k - l for k, l in zip(k33, limbs(yt << 5))])))
-        want.append(("madd", _affine_add(A, (B[0], P - B[1])), 0))
-        lines.append(" ".join(map(str, ["madd"] + acc_a + limbs(xa << 5) +
-                                  [k - l for k, l in zip(k33, limbs(ya << 5))])))
-        want.append(("madd", None, 1))
-        # specials: base = acc point (double in the caller), base = -acc (identity)
-        xa, ya = A[0] * 2**256 % P, A[1] * 2**256 % P
-        lines.append(" ".join(map(str, ["madd"] + acc_a + limbs(xa << 5) + limbs(ya << 5))))
-        want.append(("madd", None, 2))
-        lines.append(" ".join(map(str, ["madd"] + acc_a + limbs(xa << 5) + limbs((P - ya) << 5))))
-        want.append(("madd", None, 1))
-        lines.append(" ".join(map(str, ["add"] + acc_a + acc_b)))
-        want.append(("add", _affine_add(A, B), 0))
-        lines.append(" ".join(map(str, ["add"] + acc_a + _acc(A, zb))))
-        want.append(("add", None, 2))
-        lines.append(" ".join(map(str, ["add"] + acc_a + _acc((A[0], P - A[1]), zb))))
-        want.append(("add", None, 1))
-        lines.append(" ".join(map(str, ["dbl"] + acc_a)))
-        want.append(("dbl", _affine_add(A, A), 0))
-        lines.append(" ".join(map(str, ["start"] + limbs(xt << 5) + limbs(yt << 5))))
-        want.append(("start", B, 0))
+    cases = point_cases(F29, rng, 12)
+    lines = [fmt(op, ops) for op, ops, _, _ in cases]
+    want = [(op, expect, special) for op, _, expect, special in cases]
     out = point_harness(lines)
     for (op, expect, special), res in zip(want, out):
-        sp, pt, vals, v = _point_of(res)
+        sp, pt, vals, v = F29.point_of(res)
         assert sp == special, (op, sp, special)
         if special:
             continue

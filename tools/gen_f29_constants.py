@@ -29,6 +29,7 @@ def main():
     print(f"constexpr uint32_t kPinv32 = 0x{pow(P, -1, 1 << 32):08x}u;  // p^-1 mod 2^32 (zero test)")
     print(fmt("kK4", raised(4, 1), "4p, low limbs raised by 2^29 (>= 2^29 - 1)"))
     print(fmt("kK8", raised(8, 4), "8p, low limbs raised by 2^31 (>= 2^31 - 4)"))
+    print(fmt("kK8r1", raised(8, 1), "8p, low limbs raised by 2^29 (minus a normalized value < 8p)"))
     print(fmt("kK16", raised(16, 1), "16p, low limbs raised by 2^29"))
     print(fmt("kK33", raised(33, 1), "33p, low limbs raised by 2^29 (minus a normalized value < 32p)"))
     print(fmt("kK32r3", raised(32, 3), "32p, low limbs raised by 3 2^29"))

@@ -110,7 +110,9 @@ def shoup_q(w):
 
 
 def reduce(a):
-    """value - q p, q from the top two limbs (float32 as on the device),
+    """value - q p, q from the top two limbs in float32 (the host build's two
+    roundings of l8 2^29 + l7; the device fuses them into one, which gives the
+    same number since the product is exact -- tests/limb_model.py models both),
     signed carries: normalized limbs, value < 3p."""
     import struct
     f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]
