@@ -358,6 +358,54 @@ TACHYON_C_EXPORT void tachyon_mi355x_ntt_domain_transform_device(tachyon_mi355x_
                                                                 size_t batch, int inverse);
 TACHYON_C_EXPORT void* tachyon_mi355x_ntt_domain_stream(tachyon_mi355x_ntt_domain* d);
 
+/* The drop-in IcicleNTT engine (icicle_ntt.h:43-87, icicle_ntt_bn254.cc:31-101,
+ * icicle_ntt_holder.h:30-44): a holder created without a size, initialised
+ * once from a generator of order 2^LN, then serving FFT / IFFT of every
+ * power-of-two size <= 2^LN (w_size = group_gen^(2^LN / size)) on any coset --
+ * one holder for domain_ and extended_domain_ (zk/base/entities/entity.h:83-95).
+ * field: 1 bn254 Fr, 3 bls12_381 Fr (NULL for another id); stream: a
+ * hipStream_t, or NULL for a stream the handle owns.  Single device (the
+ * current one).  Every int-returning call returns 1 on success and 0 on
+ * refusal; nothing aborts, and a refused _run leaves inout untouched.
+ *   _init: group_gen_mont (32 bytes, Montgomery) must have order exactly
+ *     2^LN, 0 <= LN <= min(two-adicity, 30).  options (NULL: the defaults
+ *     below): batch_size >= 1, columns_batch == 0, ordering == 0 (natural to
+ *     natural), are_inputs_on_device == are_outputs_on_device;
+ *     fast_twiddles_mode is ignored.  On an initialised handle: 1 for the same
+ *     generator (nothing changes), 0 for another.
+ *   _run: in place on batch_size contiguous transforms of `size` elements
+ *     (Montgomery form, natural order in and out), size a power of two in
+ *     [1, 2^LN].  coset_canonical: 32 little-endian bytes, canonical form
+ *     (F::ToBigInt()), 1 = no coset; 0 and values >= the modulus are refused.
+ *     algorithm (0 Auto, 1 Radix2, 2 MixedRadix) does not change the result.
+ *     Host data: copied in and out, synchronised.  Device data: on _stream,
+ *     synchronised unless is_async; coset tables are built on the device and
+ *     the last 8 (size, coset) pairs are kept.
+ *   _release frees the tables (then _run refuses and _init works again);
+ *   _log_order: LN, or -1 when not initialised; _table_bytes: device bytes of
+ *   the stage, 29-bit and cached coset tables. */
+typedef struct tachyon_mi355x_icicle_ntt tachyon_mi355x_icicle_ntt;
+typedef struct {
+  int fast_twiddles_mode;    /* default 1 */
+  int batch_size;            /* default 1 */
+  int columns_batch;         /* default 0 */
+  int ordering;              /* default 0 = kNN */
+  int are_inputs_on_device;  /* default 0 */
+  int are_outputs_on_device; /* default 0 */
+  int is_async;              /* default 0 */
+} tachyon_mi355x_icicle_ntt_options;
+TACHYON_C_EXPORT tachyon_mi355x_icicle_ntt* tachyon_mi355x_icicle_ntt_create(int field, void* stream);
+TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_init(tachyon_mi355x_icicle_ntt* h, const void* group_gen_mont,
+                                                    const tachyon_mi355x_icicle_ntt_options* options);
+TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_run(tachyon_mi355x_icicle_ntt* h, int algorithm,
+                                                   const void* coset_canonical, void* inout, size_t size,
+                                                   int inverse);
+TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_release(tachyon_mi355x_icicle_ntt* h);
+TACHYON_C_EXPORT void tachyon_mi355x_icicle_ntt_destroy(tachyon_mi355x_icicle_ntt* h);
+TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_log_order(const tachyon_mi355x_icicle_ntt* h);
+TACHYON_C_EXPORT void* tachyon_mi355x_icicle_ntt_stream(tachyon_mi355x_icicle_ntt* h);
+TACHYON_C_EXPORT size_t tachyon_mi355x_icicle_ntt_table_bytes(const tachyon_mi355x_icicle_ntt* h);
+
 /* ---- communicators and library-level sharded entry points ------------------
  * One process per MI355X: a multi-process C/C++ caller (benchmark/msm/
  * msm_benchmark_gpu.cc:57-69 or vendors/circom/prover_main.cc:116-128 under a

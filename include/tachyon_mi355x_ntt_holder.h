@@ -30,7 +30,13 @@
  * field-generic domain (tachyon_mi355x_ntt_domain_*, bn254 Fr too):
  *
  *   auto holder = tachyon_mi355x::FieldNTTHolder<tachyon_mi355x::kBls12_381Fr>::Create(size);
- *   holder->FFT(evals, &offset);   // bls12_381::Fr, nullptr = no coset */
+ *   holder->FFT(evals, &offset);   // bls12_381::Fr, nullptr = no coset
+ *
+ * The holders above bind one size.  IcicleNTTHolder<F, kField> / IcicleNTT<F,
+ * kField> at the end of this header are the reference's holder unchanged:
+ * Create() without a size, Init(group_gen) once, FFT / IFFT(algorithm,
+ * canonical coset, container) at any power-of-two size up to the generator's
+ * order, bool results. */
 #ifndef TACHYON_MI355X_NTT_HOLDER_H_
 #define TACHYON_MI355X_NTT_HOLDER_H_
 
@@ -38,6 +44,8 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "tachyon_mi355x.h"
@@ -177,6 +185,130 @@ class NTTHolder {
  private:
   explicit NTTHolder(std::unique_ptr<NTT> ntt) : ntt_(std::move(ntt)) {}
   std::unique_ptr<NTT> ntt_;
+};
+
+/* ---- the drop-in holder: Create() without a size, Init(group_gen) once, then
+ * FFT / IFFT of any power-of-two size the initialised domain contains, the
+ * canonical coset given per call (tachyon_mi355x_icicle_ntt_*).  A Tachyon
+ * build keeps the reference's lines unchanged --
+ *
+ *   CHECK((*icicle_)->FFT(FFTAlgorithmToIcicleNTTAlgorithm(GetAlgorithm()),
+ *                         offset_big_int_, evals));
+ *   icicle_ntt_holder_ = math::IcicleNTTHolder<F>::Create();
+ *   CHECK(icicle_ntt_holder_->Init(extended_domain_->group_gen()));
+ *
+ * -- with math::IcicleNTTHolder<F> aliased to
+ * tachyon_mi355x::IcicleNTTHolder<F, kField> and ::ntt to
+ * tachyon_mi355x::ntt. */
+namespace ntt {
+/* icicle's ntt.cu.h enumerations, in its order */
+enum class NTTDir { kForward, kInverse };
+enum class Ordering { kNN, kNR, kRN, kRR, kNM, kMN };
+enum class NttAlgorithm { Auto, Radix2, MixedRadix };
+}  // namespace ntt
+
+/* icicle_ntt.h:43-51, the reference's fields and defaults.  Supported:
+ * batch_size >= 1, columns_batch false, ordering kNN, inputs and outputs both
+ * on the host or both on the device; Init refuses anything else. */
+struct IcicleNTTOptions {
+  bool fast_twiddles_mode = true;
+  int batch_size = 1;
+  bool columns_batch = false;
+  ntt::Ordering ordering = ntt::Ordering::kNN;
+  bool are_inputs_on_device = false;
+  bool are_outputs_on_device = false;
+  bool is_async = false;
+};
+
+/* IcicleNTT<F> (icicle_ntt.h:53-102) for the field kField; F: 4 x uint64
+ * Montgomery limbs.  BigInt (F::BigIntTy in the reference) is any 32-byte
+ * trivially copyable type holding the canonical little-endian value. */
+template <class F, int kField>
+class IcicleNTT {
+ public:
+  IcicleNTT() : handle_(tachyon_mi355x_icicle_ntt_create(kField, nullptr)) {}
+  explicit IcicleNTT(void* stream) : handle_(tachyon_mi355x_icicle_ntt_create(kField, stream)) {}
+  IcicleNTT(const IcicleNTT&) = delete;
+  IcicleNTT& operator=(const IcicleNTT&) = delete;
+  ~IcicleNTT() { tachyon_mi355x_icicle_ntt_destroy(handle_); }
+
+  [[nodiscard]] bool Init(const F& group_gen, const IcicleNTTOptions& options = IcicleNTTOptions()) {
+    static_assert(sizeof(F) == 4 * sizeof(uint64_t), "F must be 4 x uint64 Montgomery limbs");
+    tachyon_mi355x_icicle_ntt_options o;
+    o.fast_twiddles_mode = options.fast_twiddles_mode ? 1 : 0;
+    o.batch_size = options.batch_size;
+    o.columns_batch = options.columns_batch ? 1 : 0;
+    o.ordering = static_cast<int>(options.ordering);
+    o.are_inputs_on_device = options.are_inputs_on_device ? 1 : 0;
+    o.are_outputs_on_device = options.are_outputs_on_device ? 1 : 0;
+    o.is_async = options.is_async ? 1 : 0;
+    return handle_ && tachyon_mi355x_icicle_ntt_init(handle_, &group_gen, &o) == 1;
+  }
+
+  template <class BigInt, class Evals>
+  [[nodiscard]] bool FFT(ntt::NttAlgorithm algorithm, const BigInt& coset, Evals& evals) const {
+    const std::vector<F>& evaluations = evals.evaluations();
+    return Run(algorithm, coset, const_cast<F*>(evaluations.data()), static_cast<int>(evaluations.size()),
+               ntt::NTTDir::kForward);
+  }
+
+  template <class BigInt, class Poly>
+  [[nodiscard]] bool IFFT(ntt::NttAlgorithm algorithm, const BigInt& coset, Poly& poly) const {
+    const std::vector<F>& coefficients = poly.coefficients().coefficients();
+    return Run(algorithm, coset, const_cast<F*>(coefficients.data()), static_cast<int>(coefficients.size()),
+               ntt::NTTDir::kInverse);
+  }
+
+  /* size: elements per transform; inout holds batch_size * size of them */
+  template <class BigInt>
+  [[nodiscard]] bool Run(ntt::NttAlgorithm algorithm, const BigInt& coset, F* inout, int size,
+                         ntt::NTTDir dir) const {
+    static_assert(sizeof(BigInt) == 32 && std::is_trivially_copyable<BigInt>::value,
+                  "BigInt must hold 32 little-endian bytes");
+    if (!handle_ || size < 0) return false;
+    return tachyon_mi355x_icicle_ntt_run(handle_, static_cast<int>(algorithm), &coset, inout,
+                                         static_cast<size_t>(size), dir == ntt::NTTDir::kInverse ? 1 : 0) == 1;
+  }
+
+  [[nodiscard]] bool Release() { return handle_ && tachyon_mi355x_icicle_ntt_release(handle_) == 1; }
+
+  /* log2 of the initialised order, -1 before Init / after Release */
+  int log_order() const { return handle_ ? tachyon_mi355x_icicle_ntt_log_order(handle_) : -1; }
+  void* stream() const { return handle_ ? tachyon_mi355x_icicle_ntt_stream(handle_) : nullptr; }
+  tachyon_mi355x_icicle_ntt* handle() { return handle_; }
+
+ private:
+  tachyon_mi355x_icicle_ntt* handle_ = nullptr;
+};
+
+/* IcicleNTTHolder<F> (icicle_ntt_holder.h:15-63): empty when default
+ * constructed, Create() makes the IcicleNTT; move-only. */
+template <class F, int kField>
+class IcicleNTTHolder {
+ public:
+  IcicleNTTHolder() = default;
+  IcicleNTTHolder(IcicleNTTHolder&&) = default;
+  IcicleNTTHolder& operator=(IcicleNTTHolder&&) = default;
+
+  const IcicleNTT<F, kField>& operator*() const { return *get(); }
+  IcicleNTT<F, kField>& operator*() { return *get(); }
+
+  const IcicleNTT<F, kField>* operator->() const { return get(); }
+  IcicleNTT<F, kField>* operator->() { return get(); }
+
+  operator bool() const { return !!icicle_; }
+
+  const IcicleNTT<F, kField>* get() const { return icicle_.get(); }
+  IcicleNTT<F, kField>* get() { return icicle_.get(); }
+
+  static IcicleNTTHolder Create() { return IcicleNTTHolder(std::make_unique<IcicleNTT<F, kField>>()); }
+
+  void Release() { icicle_.reset(); }
+
+ private:
+  explicit IcicleNTTHolder(std::unique_ptr<IcicleNTT<F, kField>> icicle) : icicle_(std::move(icicle)) {}
+
+  std::unique_ptr<IcicleNTT<F, kField>> icicle_;
 };
 
 }  // namespace tachyon_mi355x

@@ -191,6 +191,15 @@ SIGNATURES = [
     ("tachyon_mi355x_ntt_domain_transform_host", None, [vp, vp, sz, i32]),
     ("tachyon_mi355x_ntt_domain_transform_device", None, [vp, vp, sz, i32]),
     ("tachyon_mi355x_ntt_domain_stream", vp, [vp]),
+    # the drop-in IcicleNTT engine (Init from a generator, any size up to its order)
+    ("tachyon_mi355x_icicle_ntt_create", vp, [i32, vp]),
+    ("tachyon_mi355x_icicle_ntt_init", i32, [vp, vp, vp]),
+    ("tachyon_mi355x_icicle_ntt_run", i32, [vp, i32, vp, vp, sz, i32]),
+    ("tachyon_mi355x_icicle_ntt_release", i32, [vp]),
+    ("tachyon_mi355x_icicle_ntt_destroy", None, [vp]),
+    ("tachyon_mi355x_icicle_ntt_log_order", i32, [vp]),
+    ("tachyon_mi355x_icicle_ntt_stream", vp, [vp]),
+    ("tachyon_mi355x_icicle_ntt_table_bytes", sz, [vp]),
     # communicators and library-level sharded entry points
     ("tachyon_mi355x_comm_unique_id", i32, [vp, sz]),
     ("tachyon_mi355x_comm_init_rccl", vp, [vp, i32, i32]),

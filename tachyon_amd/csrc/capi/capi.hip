@@ -23,6 +23,7 @@
 #include "../msm/msm_multi.h"
 #include "../ntt/ntt.h"
 #include "../util/device_ops.h"
+#include "icicle_ntt_validate.h"
 
 using namespace tachyon_amd;
 
@@ -1263,6 +1264,136 @@ void* tachyon_mi355x_ntt_domain_stream(tachyon_mi355x_ntt_domain* d) {
   void* s = nullptr;
   ntt_dispatch(d, [&](auto& dom) { s = static_cast<void*>(dom.stream()); });
   return s;
+}
+
+}  // extern "C"
+
+// ---- the drop-in IcicleNTT engine (include/tachyon_mi355x.h) ----
+// IcicleNTT<F>::Init / Run / Release (icicle_ntt.h:43-87,
+// icicle_ntt_bn254.cc:31-116) over ntt::NttGenDomain: bool results, nothing
+// aborts across this boundary.
+struct tachyon_mi355x_icicle_ntt {
+  int field = 0;
+  std::unique_ptr<ntt::NttGenDomain<Bn254Fr>> bn;
+  std::unique_ptr<ntt::NttGenDomain<Bls381Fr>> bls;
+  tachyon_mi355x_icicle_ntt_options options = icicle_ntt::default_options();
+};
+
+namespace {
+template <class Fn>
+void icicle_ntt_dispatch(const tachyon_mi355x_icicle_ntt* h, Fn&& fn) {
+  if (h->bn) fn(*h->bn);
+  else fn(*h->bls);
+}
+}  // namespace
+
+extern "C" {
+
+tachyon_mi355x_icicle_ntt* tachyon_mi355x_icicle_ntt_create(int field, void* stream) {
+  if (field != 1 && field != 3) return nullptr;
+  try {
+    auto h = std::make_unique<tachyon_mi355x_icicle_ntt>();
+    h->field = field;
+    if (field == 1) h->bn = std::make_unique<ntt::NttGenDomain<Bn254Fr>>(static_cast<hipStream_t>(stream));
+    else h->bls = std::make_unique<ntt::NttGenDomain<Bls381Fr>>(static_cast<hipStream_t>(stream));
+    return h.release();
+  } catch (...) {
+    return nullptr;
+  }
+}
+
+int tachyon_mi355x_icicle_ntt_init(tachyon_mi355x_icicle_ntt* h, const void* group_gen_mont,
+                                   const tachyon_mi355x_icicle_ntt_options* options) {
+  if (!h || !group_gen_mont) return 0;
+  const tachyon_mi355x_icicle_ntt_options opt = options ? *options : icicle_ntt::default_options();
+  if (!icicle_ntt::options_ok(opt)) return 0;
+  int ok = 0;
+  bool fresh = false;
+  try {
+    icicle_ntt_dispatch(h, [&](auto& dom) {
+      using Fr = std::decay_t<decltype(dom.group_gen())>;
+      uint32_t w[8];
+      icicle_ntt::load_words(group_gen_mont, w);
+      if (!icicle_ntt::below(w, Fr::Config::kP32)) return;  // not a Montgomery representative
+      Fr g;
+      for (int i = 0; i < 8; ++i) g.v[i] = w[i];
+      fresh = !dom.initialised();
+      ok = dom.init(g) ? 1 : 0;
+    });
+  } catch (...) {
+    return 0;
+  }
+  if (ok && fresh) h->options = opt;  // (the same generator again: nothing changes)
+  return ok;
+}
+
+int tachyon_mi355x_icicle_ntt_run(tachyon_mi355x_icicle_ntt* h, int algorithm, const void* coset_canonical,
+                                  void* inout, size_t size, int inverse) {
+  (void)algorithm;  // Auto / Radix2 / MixedRadix: one network, one result
+  if (!h || !coset_canonical || !inout) return 0;
+  int ok = 0;
+  try {
+    icicle_ntt_dispatch(h, [&](auto& dom) {
+      using Fr = std::decay_t<decltype(dom.group_gen())>;
+      const int log_m = icicle_ntt::size_log(size, dom.log_order());
+      if (log_m < 0) return;
+      uint32_t w[8];
+      icicle_ntt::load_words(coset_canonical, w);
+      if (!icicle_ntt::coset_ok(w, Fr::Config::kP32)) return;
+      Fr c;
+      for (int i = 0; i < 8; ++i) c.v[i] = w[i];
+      const Fr coset = c.to_mont().canonical();
+      const tachyon_mi355x_icicle_ntt_options& o = h->options;
+      const size_t batch = (size_t)o.batch_size;
+      if (batch > 65535) return;
+      auto* x = static_cast<Fr*>(inout);
+      if (o.are_inputs_on_device) {
+        dom.run(x, (uint32_t)log_m, inverse != 0, batch, coset);
+        if (!o.is_async) TA_HIP(hipStreamSynchronize(dom.stream()));
+      } else {
+        dom.run_host(x, (uint32_t)log_m, inverse != 0, batch, coset);
+      }
+      ok = 1;
+    });
+  } catch (...) {
+    return 0;
+  }
+  return ok;
+}
+
+int tachyon_mi355x_icicle_ntt_release(tachyon_mi355x_icicle_ntt* h) {
+  if (!h) return 0;
+  try {
+    icicle_ntt_dispatch(h, [&](auto& dom) { dom.release(); });
+  } catch (...) {
+    return 0;
+  }
+  return 1;
+}
+
+void tachyon_mi355x_icicle_ntt_destroy(tachyon_mi355x_icicle_ntt* h) {
+  try {
+    delete h;
+  } catch (...) {
+  }
+}
+
+int tachyon_mi355x_icicle_ntt_log_order(const tachyon_mi355x_icicle_ntt* h) {
+  int l = -1;
+  if (h) icicle_ntt_dispatch(h, [&](auto& dom) { l = dom.log_order(); });
+  return l;
+}
+
+void* tachyon_mi355x_icicle_ntt_stream(tachyon_mi355x_icicle_ntt* h) {
+  void* s = nullptr;
+  if (h) icicle_ntt_dispatch(h, [&](auto& dom) { s = static_cast<void*>(dom.stream()); });
+  return s;
+}
+
+size_t tachyon_mi355x_icicle_ntt_table_bytes(const tachyon_mi355x_icicle_ntt* h) {
+  size_t b = 0;
+  if (h) icicle_ntt_dispatch(h, [&](auto& dom) { b = dom.table_bytes(); });
+  return b;
 }
 
 }  // extern "C"

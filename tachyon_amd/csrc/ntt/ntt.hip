@@ -583,6 +583,30 @@ Fr two_adic_root() {
   return r;
 }
 
+// Pass plan of a 2^log_n-point transform: ceil(L / max_stages) passes, stages
+// split evenly, as many sets per workgroup as lds_elems hold
+template <class Pass>
+std::vector<Pass> pass_plan(uint32_t log_n, uint32_t lds_elems, uint32_t max_stages) {
+  std::vector<Pass> plan;
+  if (log_n == 0) return plan;
+  uint32_t P = (log_n + max_stages - 1) / max_stages;
+  uint32_t s0 = 0;
+  for (uint32_t p = 0; p < P; ++p) {
+    uint32_t k = (log_n - s0) / (P - p);
+    Pass ps;
+    ps.s0 = s0;
+    ps.k = k;
+    ps.final_pass = (s0 + k == log_n);
+    uint32_t avail = ps.final_pass ? (log_n - k) : (log_n - s0 - k);  // log2 of sets available
+    uint32_t log_m = 0;
+    while (log_m < avail && ((2u << log_m) << k) <= lds_elems) ++log_m;
+    ps.log_m = log_m;
+    plan.push_back(ps);
+    s0 += k;
+  }
+  return plan;
+}
+
 template <class Fr>
 std::vector<Fr> host_powers(const Fr& base, const Fr& scale, size_t count) {
   std::vector<Fr> out(count);
@@ -645,6 +669,30 @@ __global__ __launch_bounds__(kBlock) void twiddle_exchange_kernel(const Fr* __re
   else out[i] = in[j] * w;
 }
 
+// The two-level power tables of a coset offset, built on the device (no host
+// vector, copy or synchronisation): thread i < lo_cnt writes lo[i] = scale
+// base^i, thread lo_cnt + j writes hi[j] = base^(j 2^bits) (j < hi_cnt), each
+// by square-and-multiply over its exponent (< 2^30).  Canonical values -- the
+// field elements NttDomain::build_powers uploads.
+template <class Fr>
+__global__ __launch_bounds__(kBlock) void coset_powers_kernel(Fr* __restrict__ lo, Fr* __restrict__ hi, Fr base,
+                                                              Fr scale, uint32_t bits, uint32_t lo_cnt,
+                                                              uint32_t hi_cnt) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= lo_cnt + hi_cnt) return;
+  const bool high = t >= lo_cnt;
+  uint32_t e = high ? (t - lo_cnt) << bits : t;
+  Fr acc = high ? Fr::one() : scale;
+  Fr b = base;
+  while (e) {
+    if (e & 1) acc = acc * b;
+    e >>= 1;
+    if (e) b = b.sqr();
+  }
+  if (high) hi[t - lo_cnt] = acc.canonical();
+  else lo[t] = acc.canonical();
+}
+
 }  // namespace
 
 template <class Fr>
@@ -660,8 +708,29 @@ NttDomain<Fr>::NttDomain(size_t num_coeffs, hipStream_t stream) : stream_(stream
     own_stream_ = true;
   }
   // w_n = root^(2^(s - log n))  (PrimeFieldBase::GetRootOfUnity, prime_field_base.h:90-130)
-  omega_ = two_adic_root<Fr>();
-  for (uint32_t i = log_n_; i < (uint32_t)Fr::Config::kTwoAdicity; ++i) omega_ = omega_.sqr();
+  Fr omega = two_adic_root<Fr>();
+  for (uint32_t i = log_n_; i < (uint32_t)Fr::Config::kTwoAdicity; ++i) omega = omega.sqr();
+  setup(omega, true);
+}
+
+template <class Fr>
+NttDomain<Fr>::NttDomain(const Fr& group_gen, uint32_t log_n, hipStream_t stream) : stream_(stream) {
+  require_gpu();
+  if (log_n > (uint32_t)Fr::Config::kTwoAdicity || log_n > 30)
+    throw std::runtime_error("tachyon_mi355x: NTT size exceeds the field's two-adicity");
+  log_n_ = log_n;
+  n_ = size_t(1) << log_n_;
+  if (!stream_) {
+    TA_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    own_stream_ = true;
+  }
+  setup(group_gen, false);
+}
+
+// The domain generated by omega (order n_): constants, pass plan and tables
+template <class Fr>
+void NttDomain<Fr>::setup(const Fr& omega, bool default_variant) {
+  omega_ = omega;
   omega_inv_ = omega_.inverse();
   size_inv_ = fr_from_u64<Fr>(n_).inverse();
   offset_ = Fr::one();
@@ -677,24 +746,7 @@ NttDomain<Fr>::NttDomain(size_t num_coeffs, hipStream_t stream) : stream_(stream
   // 2-pass 2^12 x 2^12 plan of 2^24, 128 KiB of LDS per workgroup)
   if (const char* e = getenv("TACHYON_NTT_PASS_STAGES")) max_stages = std::clamp<uint32_t>(atoi(e), 4, 12);
 #endif
-  // pass plan: ceil(L / 8) passes, stages split evenly
-  if (log_n_ > 0) {
-    uint32_t P = (log_n_ + max_stages - 1) / max_stages;
-    uint32_t s0 = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-      uint32_t k = (log_n_ - s0) / (P - p);
-      Pass ps;
-      ps.s0 = s0;
-      ps.k = k;
-      ps.final_pass = (s0 + k == log_n_);
-      uint32_t avail = ps.final_pass ? (log_n_ - k) : (log_n_ - s0 - k);  // log2 of sets available
-      uint32_t log_m = 0;
-      while (log_m < avail && ((2u << log_m) << k) <= lds_elems) ++log_m;
-      ps.log_m = log_m;
-      plan_.push_back(ps);
-      s0 += k;
-    }
-  }
+  plan_ = pass_plan<Pass>(log_n_, lds_elems, max_stages);
   pow_bits_ = (log_n_ + 1) / 2;
   // stages per register step (1 = radix-2 through LDS every stage) and the
   // other schedule overrides: A/B measurements in tuning builds only
@@ -712,7 +764,7 @@ NttDomain<Fr>::NttDomain(size_t num_coeffs, hipStream_t stream) : stream_(stream
   // forward; profiles/r04b/ntt_ab_32_vs_29_2_20_24.log).  set_variant(0)
   // forces the 32-bit passes.
   if constexpr (std::is_same_v<Fr, Bn254Fr>) {
-    if (log_n_ >= 1 && log_n_ <= 20) {
+    if (default_variant && log_n_ >= 1 && log_n_ <= 20) {
       variant_ = 1;
       build_tables29();
     }
@@ -1082,6 +1134,277 @@ void NttDomain<Fr>::inverse_host(const Fr* in, size_t len, Fr* out) {
   TA_HIP(hipStreamSynchronize(stream_));
 }
 
+// ---------------------------------------------------------------------------
+// NttGenDomain: one generator, every power-of-two size up to its order
+
+namespace {
+
+template <class Fr>
+struct CosetPtrs {
+  const Fr* lo;
+  const Fr* hi;
+  const Fr* ilo;
+  const Fr* ihi;
+};
+
+// PassArgs of pass `ps` of a 2^L-point transform, as NttDomain<Fr>(2^L)::run
+// fills them (no four-step modes): c = the coset's power tables, null = plain
+template <class Fr, class Pass>
+PassArgs<Fr> sub_pass_args(const Pass& ps, uint32_t L, bool first, bool inverse, const Fr& size_inv,
+                           const CosetPtrs<Fr>* c, uint32_t pack) {
+  PassArgs<Fr> a{};
+  a.L = L;
+  a.s0 = ps.s0;
+  a.k = ps.k;
+  a.log_m = pack ? pack : ps.log_m;
+  a.final_pass = ps.final_pass ? 1u : 0u;
+  a.pow_bits = (L + 1) / 2;
+  a.mode = 0;
+  if (first && !inverse && c) {
+    a.mode |= kLoadCoset;
+    a.load_lo = c->lo;
+    a.load_hi = c->hi;
+  }
+  if (ps.final_pass && inverse) {
+    if (c) {
+      a.mode |= kStoreCoset;
+      a.store_lo = c->ilo;
+      a.store_hi = c->ihi;
+    } else {
+      a.mode |= kStoreScale;
+      a.scale = size_inv;
+    }
+  }
+  a.pack = pack;
+  return a;
+}
+
+}  // namespace
+
+template <class Fr>
+NttGenDomain<Fr>::NttGenDomain(hipStream_t stream) : stream_(stream) {
+  require_gpu();
+  if (!stream_) {
+    TA_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    own_stream_ = true;
+  }
+}
+
+template <class Fr>
+NttGenDomain<Fr>::~NttGenDomain() {
+  release();
+  if (own_stream_) (void)hipStreamDestroy(stream_);
+}
+
+template <class Fr>
+bool NttGenDomain<Fr>::init(const Fr& group_gen) {
+  if (base_) return group_gen == gen_;
+  // the order by repeated squaring: exactly 2^ln (0 never reaches 1, an
+  // element of another order not within the field's two-adicity)
+  constexpr uint32_t kMaxLog = std::min<uint32_t>((uint32_t)Fr::Config::kTwoAdicity, 30);
+  uint32_t ln = 0;
+  for (Fr x = group_gen; !x.is_one(); x = x.sqr(), ++ln)
+    if (ln == kMaxLog) return false;
+  base_.reset(new NttDomain<Fr>(group_gen, ln, stream_));
+  log_n_ = ln;
+  gen_ = group_gen.canonical();
+  plans_.clear();
+  size_inv_.clear();
+  for (uint32_t L = 0; L <= ln; ++L) {
+    plans_.push_back(pass_plan<Pass>(L, kMaxLdsElems, kMaxPassStages));
+    size_inv_.push_back(fr_from_u64<Fr>(uint64_t(1) << L).inverse());
+  }
+  if constexpr (std::is_same_v<Fr, Bn254Fr>) {
+    // both forms for the stage-table rows any L <= 20 reads on the 29-bit
+    // passes: R'-form for the last min(N, 2^20) - 1 entries (rows >= LN - 20),
+    // Shoup for the last min(N, 2^14) - 1 (rows >= LN - 14)
+    const size_t n = size_t(1) << ln;
+    cap29m_ = std::min<size_t>(n, size_t(1) << 20);
+    cap29s_ = std::min<size_t>(n, size_t(1) << 14);
+    DeviceBuffer* bm[2] = {&t29m_fwd_, &t29m_inv_};
+    DeviceBuffer* bs[2] = {&t29s_fwd_, &t29s_inv_};
+    const Fr* mont[2] = {base_->twm_fwd_.template as<Fr>(), base_->twm_inv_.template as<Fr>()};
+    for (int dir = 0; dir < 2 && n > 1; ++dir) {
+      const uint32_t cm = (uint32_t)(cap29m_ - 1), cs = (uint32_t)(cap29s_ - 1);
+      auto* m29 = static_cast<fr29::TwMont29*>(bm[dir]->ensure(cm * sizeof(fr29::TwMont29)));
+      auto* s29 = static_cast<fr29::TwShoup29*>(bs[dir]->ensure(cs * sizeof(fr29::TwShoup29)));
+      hipLaunchKernelGGL(tw29_table_kernel, dim3(ceil_div(cm, kBlock)), dim3(kBlock), 0, stream_, m29,
+                         static_cast<fr29::TwShoup29*>(nullptr), mont[dir] + (n - cap29m_), cm, cm);
+      hipLaunchKernelGGL(tw29_table_kernel, dim3(ceil_div(cs, kBlock)), dim3(kBlock), 0, stream_,
+                         static_cast<fr29::TwMont29*>(nullptr), s29, mont[dir] + (n - cap29s_), 0u, cs);
+    }
+    TA_HIP(hipGetLastError());
+  }
+  TA_HIP(hipStreamSynchronize(stream_));
+  return true;
+}
+
+template <class Fr>
+void NttGenDomain<Fr>::release() {
+  if (stream_) (void)hipStreamSynchronize(stream_);
+  base_.reset();
+  plans_.clear();
+  size_inv_.clear();
+  log_n_ = 0;
+  cap29m_ = cap29s_ = 0;
+  for (DeviceBuffer* b : {&t29m_fwd_, &t29m_inv_, &t29s_fwd_, &t29s_inv_, &scratch_, &io_}) b->release();
+  for (CosetTables& c : cosets_) {
+    c.used = 0;
+    for (DeviceBuffer* b : {&c.lo, &c.hi, &c.ilo, &c.ihi}) b->release();
+  }
+}
+
+template <class Fr>
+size_t NttGenDomain<Fr>::table_bytes() const {
+  if (!base_) return 0;
+  size_t bytes = base_->tw_fwd_.capacity() + base_->tw_inv_.capacity() + base_->twm_fwd_.capacity() +
+                 base_->twm_inv_.capacity() + t29m_fwd_.capacity() + t29m_inv_.capacity() + t29s_fwd_.capacity() +
+                 t29s_inv_.capacity();
+  for (const CosetTables& c : cosets_) bytes += c.lo.capacity() + c.hi.capacity() + c.ilo.capacity() + c.ihi.capacity();
+  return bytes;
+}
+
+// The power tables of (log_m, h): the cached entry, or the least recently
+// used one rebuilt on the device.  An entry's buffers are allocated once, at
+// the sizes of the largest sub-domain, so a rebuild only enqueues two kernels
+// behind the passes that still read the old values.
+template <class Fr>
+const typename NttGenDomain<Fr>::CosetTables& NttGenDomain<Fr>::coset_tables(uint32_t log_m, const Fr& h) {
+  CosetTables* victim = &cosets_[0];
+  for (CosetTables& c : cosets_) {
+    if (c.used && c.log_m == log_m && c.h == h) {
+      c.used = ++tick_;
+      return c;
+    }
+    if (c.used < victim->used) victim = &c;
+  }
+  CosetTables& c = *victim;
+  const size_t lo_max = size_t(1) << ((log_n_ + 1) / 2), hi_max = size_t(1) << (log_n_ / 2);
+  Fr* lo = static_cast<Fr*>(c.lo.ensure(lo_max * sizeof(Fr)));
+  Fr* hi = static_cast<Fr*>(c.hi.ensure(hi_max * sizeof(Fr)));
+  Fr* ilo = static_cast<Fr*>(c.ilo.ensure(lo_max * sizeof(Fr)));
+  Fr* ihi = static_cast<Fr*>(c.ihi.ensure(hi_max * sizeof(Fr)));
+  const uint32_t bits = (log_m + 1) / 2;
+  const uint32_t lo_cnt = 1u << bits, hi_cnt = 1u << (log_m - bits);
+  const unsigned blocks = ceil_div((size_t)lo_cnt + hi_cnt, kBlock);
+  // forward: input i times h^i; inverse: output i times m^-1 h^-i
+  hipLaunchKernelGGL(coset_powers_kernel<Fr>, dim3(blocks), dim3(kBlock), 0, stream_, lo, hi, h, Fr::one(), bits,
+                     lo_cnt, hi_cnt);
+  hipLaunchKernelGGL(coset_powers_kernel<Fr>, dim3(blocks), dim3(kBlock), 0, stream_, ilo, ihi, h.inverse(),
+                     size_inv_[log_m], bits, lo_cnt, hi_cnt);
+  TA_HIP(hipGetLastError());
+  c.log_m = log_m;
+  c.h = h;
+  c.used = ++tick_;
+  return c;
+}
+
+template <class Fr>
+bool NttGenDomain<Fr>::uses29(uint32_t log_m) const {
+  // NttDomain's default variant: BN254 Fr on the 29-bit passes up to 2^20
+  return std::is_same_v<Fr, Bn254Fr> && log_m >= 1 && log_m <= 20;
+}
+
+// NttDomain::pack_log of a 2^log_m-point domain
+template <class Fr>
+uint32_t NttGenDomain<Fr>::pack_log(uint32_t log_m, size_t batch) const {
+  if (plans_[log_m].size() != 1 || batch < 2) return 0;
+  uint32_t p = 0;
+  while (batch % (size_t(2) << p) == 0 && ((size_t(1) << log_m) << (p + 1)) <= kMaxLdsElems) ++p;
+  return p;
+}
+
+template <class Fr>
+void NttGenDomain<Fr>::run(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const Fr& coset) {
+  if (!base_) throw std::runtime_error("tachyon_mi355x: NTT run before init");
+  if (log_m > log_n_) throw std::runtime_error("tachyon_mi355x: NTT size above the initialised domain");
+  // size 1: forward is the identity (h^0 = 1); inverse scales by 1^-1
+  if (log_m == 0 || batch == 0) return;
+  if (batch > 65535) throw std::runtime_error("tachyon_mi355x: NTT batch exceeds the grid limit");
+  const CosetTables* ct = coset.is_one() ? nullptr : &coset_tables(log_m, coset);
+  if (uses29(log_m)) run29(d_data, log_m, inverse, batch, ct);
+  else run32(d_data, log_m, inverse, batch, ct);
+}
+
+template <class Fr>
+void NttGenDomain<Fr>::run_host(Fr* data, uint32_t log_m, bool inverse, size_t batch, const Fr& coset) {
+  const size_t bytes = (batch << log_m) * sizeof(Fr);
+  Fr* d = static_cast<Fr*>(io_.ensure(bytes));
+  TA_HIP(hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, stream_));
+  run(d, log_m, inverse, batch, coset);
+  TA_HIP(hipMemcpyAsync(data, d, bytes, hipMemcpyDeviceToHost, stream_));
+  TA_HIP(hipStreamSynchronize(stream_));
+}
+
+// The 32-bit passes of NttDomain::run on the size-N tables' suffix: the table
+// base advanced by N - m, PassArgs::L = log_m
+template <class Fr>
+void NttGenDomain<Fr>::run32(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const CosetTables* ct) {
+  using Tw = typename NttTw<Fr>::type;
+  constexpr bool kShoup = !std::is_same_v<Tw, Fr>;
+  const size_t m = size_t(1) << log_m, shift = (size_t(1) << log_n_) - m;
+  const Tw* tw = (inverse ? base_->tw_inv_ : base_->tw_fwd_).template as<Tw>() + shift;
+  const Fr* twm = kShoup ? (inverse ? base_->twm_inv_ : base_->twm_fwd_).template as<Fr>() + shift
+                         : reinterpret_cast<const Fr*>(tw);
+  const std::vector<Pass>& plan = plans_[log_m];
+  Fr* scratch = plan.size() > 1 ? static_cast<Fr*>(scratch_.ensure(batch * m * sizeof(Fr))) : d_data;
+  CosetPtrs<Fr> cp{};
+  if (ct) cp = {ct->lo.template as<Fr>(), ct->hi.template as<Fr>(), ct->ilo.template as<Fr>(), ct->ihi.template as<Fr>()};
+  const uint32_t pack = pack_log(log_m, batch);
+  for (size_t p = 0; p < plan.size(); ++p) {
+    const Pass& ps = plan[p];
+    const PassArgs<Fr> a = sub_pass_args<Fr>(ps, log_m, p == 0, inverse, size_inv_[log_m], ct ? &cp : nullptr, pack);
+    const Fr* src = (p == 0) ? d_data : scratch;
+    Fr* dst = ps.final_pass ? d_data : scratch;
+    const uint32_t elems = (1u << a.log_m) << ps.k;
+    const uint32_t blocks = pack ? 1u : (uint32_t)(m / elems);
+    const uint32_t gy = (uint32_t)(batch >> pack);
+    const size_t lds = (size_t)elems * sizeof(Fr);
+    // Montgomery twiddles in the first pass, Shoup entries in the later ones (NttDomain::run)
+    if (kShoup && p > 0)
+      hipLaunchKernelGGL((dif_pass_kernel<Fr, Tw, 2>), dim3(blocks, gy), dim3(kBlock), lds, stream_, src, dst, tw, a);
+    else
+      hipLaunchKernelGGL((dif_pass_kernel<Fr, Fr, 2>), dim3(blocks, gy), dim3(kBlock), lds, stream_, src, dst, twm, a);
+    TA_HIP(hipGetLastError());
+  }
+}
+
+// The 29-bit passes of NttDomain::run29 (BN254 Fr, log_m <= 20) on the bounded
+// 29-bit tables: entry (stage s, index j) of the size-m network is entry
+// (m - (m >> s)) + j + (cap - m) of a table holding the last cap - 1 entries
+template <class Fr>
+void NttGenDomain<Fr>::run29(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const CosetTables* ct) {
+  if constexpr (std::is_same_v<Fr, Bn254Fr>) {
+    const size_t m = size_t(1) << log_m;
+    const auto* tm = (inverse ? t29m_inv_ : t29m_fwd_).template as<fr29::TwMont29>() + (cap29m_ - m);
+    const auto* ts = (inverse ? t29s_inv_ : t29s_fwd_).template as<fr29::TwShoup29>();
+    uint32_t ts_off = 0;
+    if (m <= cap29s_) ts += cap29s_ - m;
+    else ts_off = (uint32_t)(m - cap29s_);  // (later passes read stages >= k0 only: m >> k0 <= 2^14)
+    const std::vector<Pass>& plan = plans_[log_m];
+    F29* scratch = plan.size() > 1 ? static_cast<F29*>(scratch_.ensure(batch * m * sizeof(F29))) : nullptr;
+    CosetPtrs<Fr> cp{};
+    if (ct) cp = {ct->lo.template as<Fr>(), ct->hi.template as<Fr>(), ct->ilo.template as<Fr>(), ct->ihi.template as<Fr>()};
+    const uint32_t pack = pack_log(log_m, batch);
+    for (size_t p = 0; p < plan.size(); ++p) {
+      const Pass& ps = plan[p];
+      const PassArgs<Fr> a = sub_pass_args<Fr>(ps, log_m, p == 0, inverse, size_inv_[log_m], ct ? &cp : nullptr, pack);
+      const void* src = (p == 0) ? static_cast<const void*>(d_data) : scratch;
+      void* dst = ps.final_pass ? static_cast<void*>(d_data) : scratch;
+      const uint32_t elems = (1u << a.log_m) << ps.k;
+      const uint32_t blocks = pack ? 1u : (uint32_t)(m / elems);
+      const uint32_t gy = (uint32_t)(batch >> pack);
+      if (p == 0)
+        hipLaunchKernelGGL((dif29_pass_kernel<true, false, fr29::TwMont29>), dim3(blocks, gy), dim3(kBlock), 0, stream_,
+                           src, dst, Tw29Table<fr29::TwMont29>{tm, 0u}, a);
+      else
+        hipLaunchKernelGGL((dif29_pass_kernel<false, false, fr29::TwShoup29>), dim3(blocks, gy), dim3(kBlock), 0,
+                           stream_, src, dst, Tw29Table<fr29::TwShoup29>{ts, ts_off}, a);
+      TA_HIP(hipGetLastError());
+    }
+  }
+}
+
 template <class Fr>
 Ntt4Step<Fr>::Ntt4Step(uint32_t log_n, uint32_t log_world, uint32_t rank, hipStream_t stream, uint32_t log_r)
     : log_n_(log_n), log_g_(log_world), rank_(rank), n_(size_t(1) << log_n), stream_(stream) {
@@ -1421,6 +1744,8 @@ Fr field_from_u64(uint64_t v) {
 
 template class NttDomain<Bn254Fr>;
 template class NttDomain<Bls381Fr>;
+template class NttGenDomain<Bn254Fr>;
+template class NttGenDomain<Bls381Fr>;
 template Bn254Fr root_of_unity<Bn254Fr>(uint32_t);
 template Bls381Fr root_of_unity<Bls381Fr>(uint32_t);
 template Bn254Fr field_from_u64<Bn254Fr>(uint64_t);

@@ -244,6 +244,86 @@ class FieldEvaluationDomain:
         return lib().tachyon_mi355x_ntt_domain_stream(self._d)
 
 
+class IcicleNTTOptions(ctypes.Structure):
+    """tachyon_mi355x_icicle_ntt_options: IcicleNTTOptions (icicle_ntt.h:43-51)
+    with the reference's defaults."""
+    _fields_ = [("fast_twiddles_mode", ctypes.c_int), ("batch_size", ctypes.c_int), ("columns_batch", ctypes.c_int),
+                ("ordering", ctypes.c_int), ("are_inputs_on_device", ctypes.c_int),
+                ("are_outputs_on_device", ctypes.c_int), ("is_async", ctypes.c_int)]
+
+    def __init__(self, fast_twiddles_mode=1, batch_size=1, columns_batch=0, ordering=0, are_inputs_on_device=0,
+                 are_outputs_on_device=0, is_async=0):
+        super().__init__(int(fast_twiddles_mode), int(batch_size), int(columns_batch), int(ordering),
+                         int(are_inputs_on_device), int(are_outputs_on_device), int(is_async))
+
+
+class IcicleNTT:
+    """IcicleNTT<F> as the reference shapes it (icicle_ntt.h:53-102) over
+    tachyon_mi355x_icicle_ntt_*: created without a size, init(group_gen) once,
+    then run() at any power-of-two size up to the generator's order, the coset
+    given per call in canonical form.  Every method returns True / False like
+    the reference's bool results; nothing raises on a refusal."""
+    AUTO, RADIX2, MIXED_RADIX = 0, 1, 2
+
+    def __init__(self, field: str, stream: int = None):
+        if field not in NTT_FIELDS:
+            raise ValueError(f"no GPU NTT for {field}")
+        self.field = field
+        self._h = lib().tachyon_mi355x_icicle_ntt_create(NTT_FIELDS[field], stream)
+        if not self._h:
+            raise RuntimeError("IcicleNTT creation failed")
+
+    def close(self):
+        if self._h:
+            lib().tachyon_mi355x_icicle_ntt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def init(self, group_gen_mont: bytes, options: IcicleNTTOptions = None) -> bool:
+        gen = ctypes.create_string_buffer(bytes(group_gen_mont), FR_BYTES)
+        return lib().tachyon_mi355x_icicle_ntt_init(self._h, gen, ctypes.byref(options) if options else None) == 1
+
+    def run_ptr(self, ptr: int, size: int, coset: int = 1, inverse: bool = False, algorithm: int = 0) -> bool:
+        """In place on the buffer at `ptr` (host or device, as the options
+        say): batch_size transforms of `size` elements; coset: the canonical
+        offset as an integer or 32 little-endian bytes (1 = no coset)."""
+        cb = coset if isinstance(coset, (bytes, bytearray)) else int(coset).to_bytes(FR_BYTES, "little")
+        return lib().tachyon_mi355x_icicle_ntt_run(self._h, algorithm, ctypes.create_string_buffer(bytes(cb), FR_BYTES),
+                                                   ptr, size, 1 if inverse else 0) == 1
+
+    def run(self, data: bytes, size: int, coset: int = 1, inverse: bool = False, algorithm: int = 0):
+        """Host data: returns the transformed bytes, or None when refused."""
+        buf = ctypes.create_string_buffer(bytes(data), max(1, len(data)))
+        ok = self.run_ptr(ctypes.addressof(buf), size, coset, inverse, algorithm)
+        return buf.raw[:len(data)] if ok else None
+
+    def fft(self, coeffs: bytes, size: int, coset: int = 1, algorithm: int = 0):
+        return self.run(coeffs, size, coset, False, algorithm)
+
+    def ifft(self, evals: bytes, size: int, coset: int = 1, algorithm: int = 0):
+        return self.run(evals, size, coset, True, algorithm)
+
+    def release(self) -> bool:
+        return lib().tachyon_mi355x_icicle_ntt_release(self._h) == 1
+
+    @property
+    def log_order(self) -> int:
+        return lib().tachyon_mi355x_icicle_ntt_log_order(self._h)
+
+    @property
+    def stream(self) -> int:
+        return lib().tachyon_mi355x_icicle_ntt_stream(self._h)
+
+    @property
+    def table_bytes(self) -> int:
+        return lib().tachyon_mi355x_icicle_ntt_table_bytes(self._h)
+
+
 class FourStepNtt:
     """One rank's plan of the distributed four-step NTT (include/tachyon_mi355x.h,
     tachyon_mi355x_bn254_ntt4_*).  n = 2^log_n = R*C, R = 2^floor(log_n/2), or
