@@ -363,7 +363,7 @@ TACHYON_C_EXPORT void* tachyon_mi355x_ntt_domain_stream(tachyon_mi355x_ntt_domai
  * once from a generator of order 2^LN, then serving FFT / IFFT of every
  * power-of-two size <= 2^LN (w_size = group_gen^(2^LN / size)) on any coset --
  * one holder for domain_ and extended_domain_ (zk/base/entities/entity.h:83-95).
- * field: 1 bn254 Fr, 3 bls12_381 Fr (NULL for another id); stream: a
+ * field: 1 bn254 Fr, 3 bls12_381 Fr, 4 baby_bear (below; NULL for another id); stream: a
  * hipStream_t, or NULL for a stream the handle owns.  Single device (the
  * current one).  Every int-returning call returns 1 on success and 0 on
  * refusal; nothing aborts, and a refused _run leaves inout untouched.
@@ -405,6 +405,44 @@ TACHYON_C_EXPORT void tachyon_mi355x_icicle_ntt_destroy(tachyon_mi355x_icicle_nt
 TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_log_order(const tachyon_mi355x_icicle_ntt* h);
 TACHYON_C_EXPORT void* tachyon_mi355x_icicle_ntt_stream(tachyon_mi355x_icicle_ntt* h);
 TACHYON_C_EXPORT size_t tachyon_mi355x_icicle_ntt_table_bytes(const tachyon_mi355x_icicle_ntt* h);
+
+/* Field 4 = baby_bear (IcicleNTT<BabyBear>, icicle_ntt_baby_bear.cc:31-115;
+ * p = 2^31 - 2^27 + 1, one uint32 Montgomery word with R = 2^32) for the
+ * tachyon_mi355x_icicle_ntt_* entries only (tachyon_mi355x_ntt_domain_create(4)
+ * stays NULL).  As documented above, except:
+ *   elements and group_gen_mont are 4 bytes (group_gen_mont < p), LN <= 27;
+ *   coset_canonical is 8 little-endian bytes (the reference's BigInt<1>) with
+ *     a value in [1, p): 0, values >= p and any bit above 32 are refused;
+ *   columns_batch may be 1: _run then treats inout as a size x batch_size
+ *     row-major matrix and transforms every column;
+ *   the passes index with 32 bits: size * batch_size, rows * cols and
+ *     (rows << added_bits) * cols must be below 2^32, anything larger is refused;
+ *   _table_bytes: the two-level twiddle tables and the cached coset tables
+ *     (96 KiB per base, under 1 MiB in all, at LN = 27; no table grows with 2^LN / 2).
+ * The two entries below are valid for field 4 only and return 0 for a handle
+ * of another field.
+ *   _run_matrix: Radix2EvaluationDomain::FFTBatch (radix2_evaluation_domain.h:
+ *     99-127) and its inverse: in place on every column of a rows x cols
+ *     row-major matrix (element (i, c) at i * cols + c), rows a power of two in
+ *     [1, 2^LN], cols >= 1; the handle's batch_size / columns_batch are
+ *     ignored, its residency and is_async apply.
+ *   _coset_lde_batch: CosetLDEBatch with reverse_at_last
+ *     (radix2_evaluation_domain.h:129-197, naive_batch_fft.h:68-121).  Per
+ *     column: the inverse transform at `rows` on the plain domain, coefficient
+ *     j times shift^j / rows, zero padding to rows << added_bits, the forward
+ *     transform at that size; natural order.  `in` (rows x cols) is not
+ *     written, `out` holds (rows << added_bits) x cols.  Refused: rows not a
+ *     power of two, rows << added_bits above 2^LN, cols == 0, a shift (8
+ *     bytes, canonical) outside [1, p), in == out with added_bits > 0
+ *     (added_bits == 0 in place is allowed).
+ *   _last_launches: kernel launches of the last transform on the handle. */
+TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_run_matrix(tachyon_mi355x_icicle_ntt* h, int algorithm,
+                                                          const void* coset_canonical, void* inout, size_t rows,
+                                                          size_t cols, int inverse);
+TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_coset_lde_batch(tachyon_mi355x_icicle_ntt* h, const void* in,
+                                                               size_t rows, size_t cols, size_t added_bits,
+                                                               const void* shift_canonical, void* out);
+TACHYON_C_EXPORT unsigned tachyon_mi355x_icicle_ntt_last_launches(const tachyon_mi355x_icicle_ntt* h);
 
 /* ---- communicators and library-level sharded entry points ------------------
  * One process per MI355X: a multi-process C/C++ caller (benchmark/msm/

@@ -113,8 +113,23 @@ class NTT {
   bool have_coset_ = false;
 };
 
-/* Field ids of tachyon_mi355x_ntt_domain_create. */
-enum NttField : int { kBn254Fr = 1, kBls12_381Fr = 3 };
+/* Field ids of tachyon_mi355x_ntt_domain_create (1 and 3) and of
+ * tachyon_mi355x_icicle_ntt_create (all three). */
+enum NttField : int { kBn254Fr = 1, kBls12_381Fr = 3, kBabyBear = 4 };
+
+/* Element and canonical BigInt sizes of a field id: 4 x uint64 Montgomery
+ * limbs and a 32-byte BigInt for the two Fr fields; one uint32 Montgomery word
+ * and the 8-byte BigInt<1> for BabyBear. */
+template <int kField>
+struct NttFieldTraits {
+  static constexpr size_t kElementBytes = 32;
+  static constexpr size_t kBigIntBytes = 32;
+};
+template <>
+struct NttFieldTraits<kBabyBear> {
+  static constexpr size_t kElementBytes = 4;
+  static constexpr size_t kBigIntBytes = 8;
+};
 
 /* IcicleNTT<F> over the field-generic domain: the same FFT / IFFT / Run as
  * NTT above for the field kField (F: 4 x uint64 Montgomery limbs). */
@@ -208,8 +223,9 @@ enum class NttAlgorithm { Auto, Radix2, MixedRadix };
 }  // namespace ntt
 
 /* icicle_ntt.h:43-51, the reference's fields and defaults.  Supported:
- * batch_size >= 1, columns_batch false, ordering kNN, inputs and outputs both
- * on the host or both on the device; Init refuses anything else. */
+ * batch_size >= 1, columns_batch false (kBabyBear: also true, the buffer is
+ * then a size x batch_size row-major matrix), ordering kNN, inputs and outputs
+ * both on the host or both on the device; Init refuses anything else. */
 struct IcicleNTTOptions {
   bool fast_twiddles_mode = true;
   int batch_size = 1;
@@ -220,9 +236,13 @@ struct IcicleNTTOptions {
   bool is_async = false;
 };
 
-/* IcicleNTT<F> (icicle_ntt.h:53-102) for the field kField; F: 4 x uint64
- * Montgomery limbs.  BigInt (F::BigIntTy in the reference) is any 32-byte
- * trivially copyable type holding the canonical little-endian value. */
+/* IcicleNTT<F> (icicle_ntt.h:53-102) for the field kField; F has the
+ * field's element size (NttFieldTraits: 4 x uint64 Montgomery limbs, or one
+ * uint32 Montgomery word for kBabyBear).  BigInt (F::BigIntTy in the
+ * reference) is any trivially copyable type of the field's BigInt size holding
+ * the canonical little-endian value.  With kBabyBear, options.columns_batch is
+ * supported and FFTBatch / CosetLDEBatch below are available
+ * (IcicleNTTHolder<BabyBear, kBabyBear>). */
 template <class F, int kField>
 class IcicleNTT {
  public:
@@ -233,7 +253,8 @@ class IcicleNTT {
   ~IcicleNTT() { tachyon_mi355x_icicle_ntt_destroy(handle_); }
 
   [[nodiscard]] bool Init(const F& group_gen, const IcicleNTTOptions& options = IcicleNTTOptions()) {
-    static_assert(sizeof(F) == 4 * sizeof(uint64_t), "F must be 4 x uint64 Montgomery limbs");
+    static_assert(sizeof(F) == NttFieldTraits<kField>::kElementBytes,
+                  "F must have the field's element size (4 x uint64 limbs; one uint32 for kBabyBear)");
     tachyon_mi355x_icicle_ntt_options o;
     o.fast_twiddles_mode = options.fast_twiddles_mode ? 1 : 0;
     o.batch_size = options.batch_size;
@@ -263,11 +284,42 @@ class IcicleNTT {
   template <class BigInt>
   [[nodiscard]] bool Run(ntt::NttAlgorithm algorithm, const BigInt& coset, F* inout, int size,
                          ntt::NTTDir dir) const {
-    static_assert(sizeof(BigInt) == 32 && std::is_trivially_copyable<BigInt>::value,
-                  "BigInt must hold 32 little-endian bytes");
+    static_assert(sizeof(BigInt) == NttFieldTraits<kField>::kBigIntBytes &&
+                      std::is_trivially_copyable<BigInt>::value,
+                  "BigInt must hold the field's canonical little-endian bytes (32; 8 for kBabyBear)");
     if (!handle_ || size < 0) return false;
     return tachyon_mi355x_icicle_ntt_run(handle_, static_cast<int>(algorithm), &coset, inout,
                                          static_cast<size_t>(size), dir == ntt::NTTDir::kInverse ? 1 : 0) == 1;
+  }
+
+  /* Radix2EvaluationDomain::FFTBatch (radix2_evaluation_domain.h:99-127) on a
+   * raw row-major rows x cols matrix (no Eigen here): every column transformed
+   * in place on the plain domain, natural order.  kBabyBear only. */
+  [[nodiscard]] bool FFTBatch(F* mat, size_t rows, size_t cols) const {
+    static_assert(kField == kBabyBear, "FFTBatch: kBabyBear only");
+    const uint64_t one = 1;
+    return handle_ && tachyon_mi355x_icicle_ntt_run_matrix(handle_, 0, &one, mat, rows, cols, 0) == 1;
+  }
+
+  /* Radix2EvaluationDomain::CosetLDEBatch (radix2_evaluation_domain.h:129-197):
+   * in (rows x cols) -> out ((rows << added_bits) x cols), the low-degree
+   * extension of every column on the coset shift * <w>.  shift is the field
+   * element as stored (Montgomery); it is converted to the canonical value the
+   * C-ABI takes here, in the header, with one Montgomery multiplication by 1
+   * (x R^-1 mod p).  kBabyBear only. */
+  [[nodiscard]] bool CosetLDEBatch(const F* in, size_t rows, size_t cols, size_t added_bits, const F& shift,
+                                   F* out) const {
+    static_assert(kField == kBabyBear, "CosetLDEBatch: kBabyBear only");
+    static_assert(sizeof(F) == 4, "BabyBear: one uint32 Montgomery word");
+    constexpr uint32_t kP = 0x78000001u, kNInv = 0x77ffffffu; /* p, -p^-1 mod 2^32 */
+    uint32_t m;
+    std::memcpy(&m, &shift, sizeof(m));
+    const uint32_t q = m * kNInv;
+    uint32_t c = static_cast<uint32_t>((static_cast<uint64_t>(m) + static_cast<uint64_t>(q) * kP) >> 32);
+    if (c >= kP) c -= kP;
+    const uint64_t canonical = c;
+    return handle_ &&
+           tachyon_mi355x_icicle_ntt_coset_lde_batch(handle_, in, rows, cols, added_bits, &canonical, out) == 1;
   }
 
   [[nodiscard]] bool Release() { return handle_ && tachyon_mi355x_icicle_ntt_release(handle_) == 1; }

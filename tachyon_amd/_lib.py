@@ -200,6 +200,9 @@ SIGNATURES = [
     ("tachyon_mi355x_icicle_ntt_log_order", i32, [vp]),
     ("tachyon_mi355x_icicle_ntt_stream", vp, [vp]),
     ("tachyon_mi355x_icicle_ntt_table_bytes", sz, [vp]),
+    ("tachyon_mi355x_icicle_ntt_run_matrix", i32, [vp, i32, vp, vp, sz, sz, i32]),
+    ("tachyon_mi355x_icicle_ntt_coset_lde_batch", i32, [vp, vp, sz, sz, sz, vp, vp]),
+    ("tachyon_mi355x_icicle_ntt_last_launches", ctypes.c_uint, [vp]),
     # communicators and library-level sharded entry points
     ("tachyon_mi355x_comm_unique_id", i32, [vp, sz]),
     ("tachyon_mi355x_comm_init_rccl", vp, [vp, i32, i32]),

@@ -29,6 +29,23 @@ inline bool options_ok(const tachyon_mi355x_icicle_ntt_options& o) {
          (o.are_inputs_on_device != 0) == (o.are_outputs_on_device != 0);
 }
 
+// baby_bear (field 4): as above, and columns_batch 0 or 1
+inline bool options_ok_columns(const tachyon_mi355x_icicle_ntt_options& o) {
+  return o.batch_size >= 1 && (o.columns_batch == 0 || o.columns_batch == 1) && o.ordering == 0 &&
+         (o.are_inputs_on_device != 0) == (o.are_outputs_on_device != 0);
+}
+
+// baby_bear's BigInt<1>: 8 little-endian bytes holding a canonical value in
+// [1, modulus); false for 0, for values >= modulus and for any bit above 32
+inline bool small_coset(const void* bytes, uint32_t modulus, uint32_t* out) {
+  const unsigned char* b = static_cast<const unsigned char*>(bytes);
+  uint64_t v = 0;
+  for (int i = 7; i >= 0; --i) v = (v << 8) | b[i];
+  if (v == 0 || v >= modulus) return false;
+  *out = (uint32_t)v;
+  return true;
+}
+
 // log2(size) for a power of two in [1, 2^log_order], -1 for anything else
 inline int size_log(size_t size, int log_order) {
   if (log_order < 0 || size == 0 || (size & (size - 1)) != 0) return -1;

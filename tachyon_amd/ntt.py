@@ -257,19 +257,30 @@ class IcicleNTTOptions(ctypes.Structure):
                          int(are_inputs_on_device), int(are_outputs_on_device), int(is_async))
 
 
+# the holder's fields: (C-ABI field id, element bytes, canonical BigInt bytes).
+# Separate from NTT_FIELDS, which FieldEvaluationDomain also reads: baby_bear
+# exists for the holder only.
+ICICLE_NTT_FIELDS = {"bn254_fr": (1, 32, 32), "bls12_381_fr": (3, 32, 32), "baby_bear": (4, 4, 8)}
+
+
 class IcicleNTT:
     """IcicleNTT<F> as the reference shapes it (icicle_ntt.h:53-102) over
     tachyon_mi355x_icicle_ntt_*: created without a size, init(group_gen) once,
     then run() at any power-of-two size up to the generator's order, the coset
     given per call in canonical form.  Every method returns True / False like
-    the reference's bool results; nothing raises on a refusal."""
+    the reference's bool results; nothing raises on a refusal.
+
+    "baby_bear" (4-byte Montgomery words, the coset as 8 canonical bytes) also
+    takes columns_batch=1 and has run_matrix / fft_batch / ifft_batch /
+    coset_lde_batch on row-major matrices."""
     AUTO, RADIX2, MIXED_RADIX = 0, 1, 2
 
     def __init__(self, field: str, stream: int = None):
-        if field not in NTT_FIELDS:
+        if field not in ICICLE_NTT_FIELDS:
             raise ValueError(f"no GPU NTT for {field}")
         self.field = field
-        self._h = lib().tachyon_mi355x_icicle_ntt_create(NTT_FIELDS[field], stream)
+        field_id, self.element_bytes, self.bigint_bytes = ICICLE_NTT_FIELDS[field]
+        self._h = lib().tachyon_mi355x_icicle_ntt_create(field_id, stream)
         if not self._h:
             raise RuntimeError("IcicleNTT creation failed")
 
@@ -285,16 +296,27 @@ class IcicleNTT:
             pass
 
     def init(self, group_gen_mont: bytes, options: IcicleNTTOptions = None) -> bool:
-        gen = ctypes.create_string_buffer(bytes(group_gen_mont), FR_BYTES)
+        gen = ctypes.create_string_buffer(bytes(group_gen_mont), self.element_bytes)
         return lib().tachyon_mi355x_icicle_ntt_init(self._h, gen, ctypes.byref(options) if options else None) == 1
 
     def run_ptr(self, ptr: int, size: int, coset: int = 1, inverse: bool = False, algorithm: int = 0) -> bool:
         """In place on the buffer at `ptr` (host or device, as the options
         say): batch_size transforms of `size` elements; coset: the canonical
-        offset as an integer or 32 little-endian bytes (1 = no coset)."""
-        cb = coset if isinstance(coset, (bytes, bytearray)) else int(coset).to_bytes(FR_BYTES, "little")
-        return lib().tachyon_mi355x_icicle_ntt_run(self._h, algorithm, ctypes.create_string_buffer(bytes(cb), FR_BYTES),
-                                                   ptr, size, 1 if inverse else 0) == 1
+        offset as an integer or the field's little-endian BigInt bytes (1 = no
+        coset)."""
+        return lib().tachyon_mi355x_icicle_ntt_run(self._h, algorithm, self._bigint(coset), ptr, size,
+                                                   1 if inverse else 0) == 1
+
+    def _bigint(self, value):
+        """The canonical little-endian BigInt buffer of an integer (or bytes);
+        an integer too large for it is passed as all-ones, which is refused."""
+        if isinstance(value, (bytes, bytearray)):
+            raw = bytes(value)
+        else:
+            v = int(value)
+            raw = v.to_bytes(self.bigint_bytes, "little") if 0 <= v < 1 << (8 * self.bigint_bytes) else \
+                b"\xff" * self.bigint_bytes
+        return ctypes.create_string_buffer(raw, self.bigint_bytes)
 
     def run(self, data: bytes, size: int, coset: int = 1, inverse: bool = False, algorithm: int = 0):
         """Host data: returns the transformed bytes, or None when refused."""
@@ -307,6 +329,46 @@ class IcicleNTT:
 
     def ifft(self, evals: bytes, size: int, coset: int = 1, algorithm: int = 0):
         return self.run(evals, size, coset, True, algorithm)
+
+    # ---- baby_bear: row-major matrices, every column one transform ----
+    def run_matrix_ptr(self, ptr: int, rows: int, cols: int, coset: int = 1, inverse: bool = False,
+                       algorithm: int = 0) -> bool:
+        """In place on the rows x cols row-major matrix at `ptr` (host or
+        device, as the options say); batch_size / columns_batch are ignored."""
+        return lib().tachyon_mi355x_icicle_ntt_run_matrix(self._h, algorithm, self._bigint(coset), ptr, rows, cols,
+                                                          1 if inverse else 0) == 1
+
+    def run_matrix(self, data: bytes, rows: int, cols: int, coset: int = 1, inverse: bool = False, algorithm: int = 0):
+        """Host data: returns the transformed bytes, or None when refused."""
+        buf = ctypes.create_string_buffer(bytes(data), max(1, len(data)))
+        ok = self.run_matrix_ptr(ctypes.addressof(buf), rows, cols, coset, inverse, algorithm)
+        return buf.raw[:len(data)] if ok else None
+
+    def fft_batch(self, mat: bytes, rows: int, cols: int, coset: int = 1):
+        """Radix2EvaluationDomain::FFTBatch (radix2_evaluation_domain.h:99-127)."""
+        return self.run_matrix(mat, rows, cols, coset, False)
+
+    def ifft_batch(self, mat: bytes, rows: int, cols: int, coset: int = 1):
+        return self.run_matrix(mat, rows, cols, coset, True)
+
+    def coset_lde_batch_ptr(self, in_ptr: int, rows: int, cols: int, added_bits: int, shift: int, out_ptr: int) -> bool:
+        """CosetLDEBatch (radix2_evaluation_domain.h:129-197) from the rows x
+        cols matrix at in_ptr to the (rows << added_bits) x cols matrix at
+        out_ptr (host or device, as the options say); shift: canonical."""
+        return lib().tachyon_mi355x_icicle_ntt_coset_lde_batch(self._h, in_ptr, rows, cols, added_bits,
+                                                               self._bigint(shift), out_ptr) == 1
+
+    def coset_lde_batch(self, mat: bytes, rows: int, cols: int, added_bits: int, shift: int):
+        """Host data: returns the extended matrix's bytes, or None when refused."""
+        src = ctypes.create_string_buffer(bytes(mat), max(1, len(mat)))
+        out_len = len(mat) << added_bits if 0 <= added_bits < 32 else 0
+        dst = ctypes.create_string_buffer(max(1, out_len))
+        ok = self.coset_lde_batch_ptr(ctypes.addressof(src), rows, cols, added_bits, shift, ctypes.addressof(dst))
+        return dst.raw[:out_len] if ok else None
+
+    @property
+    def last_launches(self) -> int:
+        return lib().tachyon_mi355x_icicle_ntt_last_launches(self._h)
 
     def release(self) -> bool:
         return lib().tachyon_mi355x_icicle_ntt_release(self._h) == 1

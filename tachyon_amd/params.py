@@ -49,6 +49,28 @@ BLS12_381_G2 = dict(                                               # BUILD.bazel
 )
 BLS12_381_FQ2_NON_RESIDUE = -1
 
+# --- BabyBear ---------------------------------------------------------------
+# tachyon/math/finite_fields/baby_bear/BUILD.bazel (small prime field, one
+# uint32 in Montgomery form with R = 2^32).  Not in FIELDS: it has no 64-bit
+# limb layout; tools/gen_bb31_constants.py writes its header.
+BABY_BEAR = 2**31 - 2**27 + 1
+BABY_BEAR_GENERATOR = 31                 # generates the whole multiplicative group
+BABY_BEAR_TWO_ADICITY = 27
+BABY_BEAR_R = 2**32
+BABY_BEAR_BYTES = 4                      # one element
+BABY_BEAR_BIGINT_BYTES = 8               # BigInt<1>: the canonical coset / shift
+
+
+def baby_bear_root_of_unity(n: int) -> int:
+    """w_n = 31^((p-1)/n), canonical, n a power of two <= 2^27."""
+    assert n >= 1 and n & (n - 1) == 0 and n <= 1 << BABY_BEAR_TWO_ADICITY
+    return pow(BABY_BEAR_GENERATOR, (BABY_BEAR - 1) // n, BABY_BEAR)
+
+
+def baby_bear_mont(x: int) -> int:
+    return (x % BABY_BEAR) * BABY_BEAR_R % BABY_BEAR
+
+
 # name -> (modulus, 64-bit limb count, multiplicative generator or None)
 FIELDS = {
     "bn254_fq": (BN254_FQ, 4, BN254_FQ_SUBGROUP_GENERATOR),
