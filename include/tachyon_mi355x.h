@@ -444,6 +444,86 @@ TACHYON_C_EXPORT int tachyon_mi355x_icicle_ntt_coset_lde_batch(tachyon_mi355x_ic
                                                                const void* shift_canonical, void* out);
 TACHYON_C_EXPORT unsigned tachyon_mi355x_icicle_ntt_last_launches(const tachyon_mi355x_icicle_ntt* h);
 
+/* ---- Poseidon2 over BabyBear and FieldMerkleTree<BabyBear, 8> ---------------
+ * The hash side of TwoAdicFRI::Commit (two_adic_fri.h:76-94 ->
+ * FieldMerkleTreeMMCS::CommitOwned): Poseidon2 of width 16, x^7, 8 full and 13
+ * partial rounds (Poseidon2Params<BabyBear, 15, 7>, Grain LFSR constants, the
+ * Plonky3 internal layer with shifts), PaddingFreeSponge<., 8, 8> leaf hashes,
+ * TruncatedPermutation<., 8, 2> compression, FieldMerkleTree::Build with mixed
+ * heights, bytewise the reference's results.  Elements are 4-byte Montgomery
+ * words as for field 4 above; a BabyBear4 matrix is the base-field matrix with
+ * 4 x the columns.  external_matrix picks the 4 x 4 block of the external
+ * layer: 0 Horizen (5 7 1 3 / 4 6 1 1 / 1 3 5 7 / 1 1 4 6), 1 Plonky3 (the
+ * circulant 2 3 1 1).  Nothing aborts: 1 = success, 0 = refusal.
+ *
+ *   _permute: `count` states of 16 words in place.  Host states are copied
+ *     both ways and the call returns when they are back; device states are
+ *     enqueued on `stream` (waited for only when stream is NULL).
+ *   _create / _destroy: a tree on `stream` (NULL: a stream of its own).
+ *   _build: `count` row-major matrices, matrix m rows[m] x cols[m] words, host
+ *     or device memory each (hipPointerGetAttributes).  Host matrices are
+ *     uploaded and kept; device matrices are referenced, not copied: the
+ *     caller keeps them alive and unchanged for _open.  With device matrices
+ *     the call only enqueues on the tree's stream.  Matrices are stable-sorted
+ *     by height, descending; the tallest ones are hashed row by row
+ *     (concatenated in that order) into layer 0, padded with zero digests to
+ *     bit_ceil(rows); a later layer of size s takes the matrices with
+ *     bit_ceil(rows) == s as next[i] = C(C(prev[2i], prev[2i+1]), H(row i)),
+ *     the zero digest in place of H for rows <= i < s.
+ *     flags: TACHYON_MI355X_MERKLE_BIT_REVERSED makes leaf i of every matrix its
+ *     stored row bitrev(i) over log2(rows) bits: committing the natural-order
+ *     output of _icicle_ntt_coset_lde_batch with it gives the layers the
+ *     reference gets from its bit-reversed LDE, without a permuted copy.
+ *     Refused, the tree keeping what it held: null pointers, count 0, rows or
+ *     cols 0, unknown flags, heights that round up to the same power of two
+ *     but differ, the flag with a height that is not a power of two, more than
+ *     16 matrices in one layer, rows above 2^30, a row above 2^24 words.
+ *     Also 0 on a HIP error; if the layer buffer cannot be allocated the tree
+ *     is left without a build (_num_layers 0).
+ *   _num_layers: log2(bit_ceil(max rows)) + 1, 0 before a build.
+ *     _layer_size(k): digests in layer k.  _layer / _root: copies of 8-word
+ *     digests to host memory (they wait for the stream); a layer is the
+ *     reference's std::vector<std::array<F, 8>>.  _layers_device_ptr: the
+ *     layers one after another in device memory, layer 0 first.
+ *   _open (DoCreateOpeningProof): rows_out[m] receives cols[m] words, row
+ *     index >> (log_max - ceil_log2(rows[m])) of matrix m in the caller's order
+ *     (mapped through bitrev with the flag; zeros when that row is past the
+ *     height of a matrix whose height is no power of two); siblings_out
+ *     receives num_layers - 1 digests, layer[k][(index >> k) ^ 1].  Refused:
+ *     no tree built, index >= _layer_size(0), null pointers.
+ *   _last_launches: kernel launches of the last _build.
+ *   tachyon_mi355x_baby_bear_mul_rate: Montgomery products per second of
+ *     `iters` rounds of 4 chained in-register products in `threads` lanes (the
+ *     VALU yardstick of tools/poseidon2_probe.py); 0 on failure. */
+#define TACHYON_MI355X_POSEIDON2_HORIZEN 0
+#define TACHYON_MI355X_POSEIDON2_PLONKY3 1
+#define TACHYON_MI355X_MERKLE_BIT_REVERSED 1u
+typedef struct tachyon_mi355x_baby_bear_merkle_tree tachyon_mi355x_baby_bear_merkle_tree;
+TACHYON_C_EXPORT int tachyon_mi355x_poseidon2_baby_bear_permute(int external_matrix, void* states, size_t count,
+                                                                void* stream);
+TACHYON_C_EXPORT tachyon_mi355x_baby_bear_merkle_tree* tachyon_mi355x_baby_bear_merkle_tree_create(
+    int external_matrix, void* stream);
+TACHYON_C_EXPORT void tachyon_mi355x_baby_bear_merkle_tree_destroy(tachyon_mi355x_baby_bear_merkle_tree* tree);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_merkle_tree_build(tachyon_mi355x_baby_bear_merkle_tree* tree,
+                                                                const void* const* matrices, const size_t* rows,
+                                                                const size_t* cols, size_t count, unsigned flags);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_merkle_tree_root(tachyon_mi355x_baby_bear_merkle_tree* tree, void* out);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_merkle_tree_num_layers(
+    const tachyon_mi355x_baby_bear_merkle_tree* tree);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_merkle_tree_layer_size(
+    const tachyon_mi355x_baby_bear_merkle_tree* tree, size_t k);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_merkle_tree_layer(tachyon_mi355x_baby_bear_merkle_tree* tree, size_t k,
+                                                                void* out);
+TACHYON_C_EXPORT const void* tachyon_mi355x_baby_bear_merkle_tree_layers_device_ptr(
+    const tachyon_mi355x_baby_bear_merkle_tree* tree);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_merkle_tree_open(tachyon_mi355x_baby_bear_merkle_tree* tree,
+                                                               size_t index, void* const* rows_out,
+                                                               void* siblings_out);
+TACHYON_C_EXPORT unsigned tachyon_mi355x_baby_bear_merkle_tree_last_launches(
+    const tachyon_mi355x_baby_bear_merkle_tree* tree);
+TACHYON_C_EXPORT void* tachyon_mi355x_baby_bear_merkle_tree_stream(tachyon_mi355x_baby_bear_merkle_tree* tree);
+TACHYON_C_EXPORT double tachyon_mi355x_baby_bear_mul_rate(size_t threads, unsigned iters);
+
 /* ---- communicators and library-level sharded entry points ------------------
  * One process per MI355X: a multi-process C/C++ caller (benchmark/msm/
  * msm_benchmark_gpu.cc:57-69 or vendors/circom/prover_main.cc:116-128 under a

@@ -203,6 +203,22 @@ SIGNATURES = [
     ("tachyon_mi355x_icicle_ntt_run_matrix", i32, [vp, i32, vp, vp, sz, sz, i32]),
     ("tachyon_mi355x_icicle_ntt_coset_lde_batch", i32, [vp, vp, sz, sz, sz, vp, vp]),
     ("tachyon_mi355x_icicle_ntt_last_launches", ctypes.c_uint, [vp]),
+    # Poseidon2 over BabyBear and FieldMerkleTree<BabyBear, 8>
+    ("tachyon_mi355x_poseidon2_baby_bear_permute", i32, [i32, vp, sz, vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_create", vp, [i32, vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_destroy", None, [vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_build", i32, [vp, ctypes.POINTER(ctypes.c_void_p),
+                                                         ctypes.POINTER(ctypes.c_size_t),
+                                                         ctypes.POINTER(ctypes.c_size_t), sz, ctypes.c_uint]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_root", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_num_layers", sz, [vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_layer_size", sz, [vp, sz]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_layer", i32, [vp, sz, vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_layers_device_ptr", vp, [vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_open", i32, [vp, sz, ctypes.POINTER(ctypes.c_void_p), vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_last_launches", ctypes.c_uint, [vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_stream", vp, [vp]),
+    ("tachyon_mi355x_baby_bear_mul_rate", ctypes.c_double, [sz, ctypes.c_uint]),
     # communicators and library-level sharded entry points
     ("tachyon_mi355x_comm_unique_id", i32, [vp, sz]),
     ("tachyon_mi355x_comm_init_rccl", vp, [vp, i32, i32]),

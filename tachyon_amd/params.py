@@ -71,6 +71,27 @@ def baby_bear_mont(x: int) -> int:
     return (x % BABY_BEAR) * BABY_BEAR_R % BABY_BEAR
 
 
+# Poseidon2 over BabyBear as the reference configures it everywhere
+# (poseidon2_params.h, Poseidon2Params<BabyBear, 15, 7>): width 16, x^7,
+# 4 + 4 full rounds around 13 partial rounds; PaddingFreeSponge<., 8, 8> leaf
+# hashes and TruncatedPermutation<., 8, 2> compression in FieldMerkleTree<F, 8>.
+# tools/gen_poseidon2_bb_constants.py writes the round constants' header.
+POSEIDON2_BB_WIDTH = 16
+POSEIDON2_BB_ALPHA = 7
+POSEIDON2_BB_FULL_ROUNDS = 8
+POSEIDON2_BB_PARTIAL_ROUNDS = 13
+POSEIDON2_BB_RATE = 8
+POSEIDON2_BB_DIGEST = 8
+# internal layer: lane i >= 1 is S + 2^shift[i-1] v_i, lane 0 is S - 2 v_0
+POSEIDON2_BB_INTERNAL_SHIFTS = tuple(range(14)) + (15,)
+# external layer: the 4 x 4 block, by id of the C-ABI's external_matrix argument
+POSEIDON2_EXTERNAL = {"horizen": 0, "plonky3": 1}
+POSEIDON2_M4 = {
+    "horizen": ((5, 7, 1, 3), (4, 6, 1, 1), (1, 3, 5, 7), (1, 1, 4, 6)),
+    "plonky3": ((2, 3, 1, 1), (1, 2, 3, 1), (1, 1, 2, 3), (3, 1, 1, 2)),
+}
+
+
 # name -> (modulus, 64-bit limb count, multiplicative generator or None)
 FIELDS = {
     "bn254_fq": (BN254_FQ, 4, BN254_FQ_SUBGROUP_GENERATOR),
