@@ -524,6 +524,97 @@ TACHYON_C_EXPORT unsigned tachyon_mi355x_baby_bear_merkle_tree_last_launches(
 TACHYON_C_EXPORT void* tachyon_mi355x_baby_bear_merkle_tree_stream(tachyon_mi355x_baby_bear_merkle_tree* tree);
 TACHYON_C_EXPORT double tachyon_mi355x_baby_bear_mul_rate(size_t threads, unsigned iters);
 
+/* ---- BabyBear4 and the FRI opening ------------------------------------------
+ * TwoAdicFRI::CreateOpeningProof (two_adic_fri.h:96-219, prove.h,
+ * fri_config.h) without its challenger: the caller's transcript samples alpha
+ * and every beta and hands them in; each commit-phase root is handed back
+ * before the next beta is needed.  A BabyBear4 element is 4 Montgomery words
+ * c0..c3 of F[x] / (x^4 - 11), 16 bytes.  Every result is a canonical element,
+ * bytewise the reference's.  1 = success, 0 = refusal; a refusal leaves the
+ * handle as it was, except the zero-denominator one.
+ *
+ *   tachyon_mi355x_baby_bear4_ops: out[i] = a[i] op b[i] on `count` elements,
+ *     op 0 add, 1 sub, 2 mul, 3 square, 4 inverse (b is ignored by 3 and 4 and
+ *     may be NULL; the inverse of 0 is 0).  All arrays host memory (copied both
+ *     ways, the call returns when `out` is written) or all device memory
+ *     (enqueued on `stream`, waited for only when stream is NULL); out may be a
+ *     or b.  Refused: unknown op, null pointers, count 0 or above 2^28, host
+ *     and device memory mixed.
+ *   _create(log_blowup, external_matrix, stream) / _destroy: log_blowup 1..26,
+ *     external_matrix as for the tree; stream NULL: a stream of its own.
+ *   _begin(alpha): forgets everything and sets the batching challenge (4
+ *     canonical Montgomery words).
+ *   _add_round: one commit round's `count` extensions in the order of the
+ *     round's tree, matrix m rows[m] x cols[m] words in natural row order on
+ *     the coset 31 <w_rows> (what _icicle_ntt_coset_lde_batch wrote), host or
+ *     device memory each; device matrices are referenced until the next _begin.
+ *     points[m]: num_points[m] BabyBear4 opening points in host memory;
+ *     opened_values_out[m]: num_points[m] * cols[m] elements of host memory,
+ *     the values of point p at [p * cols[m] ..) (both may be NULL for a matrix
+ *     without points, which still creates its height's zero input).  Adds
+ *     alpha^offset (rr[i] - sum_c alpha^c ys[c]) / (x_i - z) to the reduced
+ *     opening of the matrix's height, offsets running across matrices, points
+ *     and rounds in the reference's order.  Waits for the stream once.
+ *     Refused: null pointers, count 0, cols 0 or above 2^24, rows no power of
+ *     two, below 2^log_blowup or above 2^27, a non-canonical point, a call
+ *     before _begin or after the first _commit.  A point inside 31 <w_rows>
+ *     (where the reference CHECKs) is found on the device: the call returns 0
+ *     and the handle refuses everything until the next _begin.
+ *   _num_inputs / _input_log_size(k) / _input(k, out) / _input_device_ptr(k):
+ *     the reduced openings, largest first, 2^log_size elements each in the
+ *     reference's (bit-reversed) order: position i belongs to natural row
+ *     bitrev(i).  _input copies to host memory and waits.
+ *   _commit(root_out): while the folded vector is longer than 2^log_blowup,
+ *     builds a FieldMerkleTree over it as size/2 rows of 8 words, copies the
+ *     8-word root to root_out (waits once) and returns 1; returns 0 once the
+ *     phase has ended.  The first call freezes the inputs.  Refused (0 as
+ *     well): no input, a root that _fold has not consumed yet.
+ *   _fold(beta): FoldMatrix with the challenge sampled after that root, plus
+ *     the input of the new size if there is one.  Only enqueues.  Refused:
+ *     no pending _commit, a non-canonical beta.
+ *   _num_commits: trees built so far.  _final_poly(out): the last 2^log_blowup
+ *     values (all equal for honest inputs; final_eval is the first), after the
+ *     phase has ended.
+ *   _answer_query(index, sibling_values_out, siblings_out) (AnswerQuery): for
+ *     commit-phase tree i, sibling_values_out[i] is element (index >> i) ^ 1 of
+ *     that step's vector, and siblings_out receives the log_max - i - 1 digests
+ *     of leaf (index >> i) >> 1, tree 0 first, each from the leaf layer up.
+ *     Refused: before the phase has ended, index >= the largest input's size.
+ *   _last_launches: kernel launches of the last _add_round, _commit, _fold or
+ *     _answer_query.  _stream: the stream everything is enqueued on. */
+typedef struct tachyon_mi355x_baby_bear_fri_opening tachyon_mi355x_baby_bear_fri_opening;
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear4_ops(int op, const void* a, const void* b, void* out, size_t count,
+                                                   void* stream);
+TACHYON_C_EXPORT tachyon_mi355x_baby_bear_fri_opening* tachyon_mi355x_baby_bear_fri_opening_create(
+    unsigned log_blowup, int external_matrix, void* stream);
+TACHYON_C_EXPORT void tachyon_mi355x_baby_bear_fri_opening_destroy(tachyon_mi355x_baby_bear_fri_opening* h);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_begin(tachyon_mi355x_baby_bear_fri_opening* h,
+                                                                const void* alpha);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_add_round(
+    tachyon_mi355x_baby_bear_fri_opening* h, const void* const* ldes, const size_t* rows, const size_t* cols,
+    size_t count, const void* const* points, const size_t* num_points, void* const* opened_values_out);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_fri_opening_num_inputs(const tachyon_mi355x_baby_bear_fri_opening* h);
+TACHYON_C_EXPORT unsigned tachyon_mi355x_baby_bear_fri_opening_input_log_size(
+    const tachyon_mi355x_baby_bear_fri_opening* h, size_t k);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_input(tachyon_mi355x_baby_bear_fri_opening* h, size_t k,
+                                                                void* out);
+TACHYON_C_EXPORT const void* tachyon_mi355x_baby_bear_fri_opening_input_device_ptr(
+    const tachyon_mi355x_baby_bear_fri_opening* h, size_t k);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_commit(tachyon_mi355x_baby_bear_fri_opening* h,
+                                                                 void* root_out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_fold(tachyon_mi355x_baby_bear_fri_opening* h,
+                                                               const void* beta);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_fri_opening_num_commits(
+    const tachyon_mi355x_baby_bear_fri_opening* h);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_final_poly(tachyon_mi355x_baby_bear_fri_opening* h,
+                                                                     void* out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_answer_query(tachyon_mi355x_baby_bear_fri_opening* h,
+                                                                       size_t index, void* sibling_values_out,
+                                                                       void* siblings_out);
+TACHYON_C_EXPORT unsigned tachyon_mi355x_baby_bear_fri_opening_last_launches(
+    const tachyon_mi355x_baby_bear_fri_opening* h);
+TACHYON_C_EXPORT void* tachyon_mi355x_baby_bear_fri_opening_stream(tachyon_mi355x_baby_bear_fri_opening* h);
+
 /* ---- communicators and library-level sharded entry points ------------------
  * One process per MI355X: a multi-process C/C++ caller (benchmark/msm/
  * msm_benchmark_gpu.cc:57-69 or vendors/circom/prover_main.cc:116-128 under a

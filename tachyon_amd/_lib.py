@@ -219,6 +219,28 @@ SIGNATURES = [
     ("tachyon_mi355x_baby_bear_merkle_tree_last_launches", ctypes.c_uint, [vp]),
     ("tachyon_mi355x_baby_bear_merkle_tree_stream", vp, [vp]),
     ("tachyon_mi355x_baby_bear_mul_rate", ctypes.c_double, [sz, ctypes.c_uint]),
+    # BabyBear4 and the FRI opening (CreateOpeningProof without its challenger)
+    ("tachyon_mi355x_baby_bear4_ops", i32, [i32, vp, vp, vp, sz, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_create", vp, [ctypes.c_uint, i32, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_destroy", None, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_begin", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_add_round", i32, [vp, ctypes.POINTER(ctypes.c_void_p),
+                                                             ctypes.POINTER(ctypes.c_size_t),
+                                                             ctypes.POINTER(ctypes.c_size_t), sz,
+                                                             ctypes.POINTER(ctypes.c_void_p),
+                                                             ctypes.POINTER(ctypes.c_size_t),
+                                                             ctypes.POINTER(ctypes.c_void_p)]),
+    ("tachyon_mi355x_baby_bear_fri_opening_num_inputs", sz, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_input_log_size", ctypes.c_uint, [vp, sz]),
+    ("tachyon_mi355x_baby_bear_fri_opening_input", i32, [vp, sz, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_input_device_ptr", vp, [vp, sz]),
+    ("tachyon_mi355x_baby_bear_fri_opening_commit", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_fold", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_num_commits", sz, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_final_poly", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_answer_query", i32, [vp, sz, vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_last_launches", ctypes.c_uint, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_stream", vp, [vp]),
     # communicators and library-level sharded entry points
     ("tachyon_mi355x_comm_unique_id", i32, [vp, sz]),
     ("tachyon_mi355x_comm_init_rccl", vp, [vp, i32, i32]),
