@@ -543,7 +543,8 @@ TACHYON_C_EXPORT double tachyon_mi355x_baby_bear_mul_rate(size_t threads, unsign
  *   _create(log_blowup, external_matrix, stream) / _destroy: log_blowup 1..26,
  *     external_matrix as for the tree; stream NULL: a stream of its own.
  *   _begin(alpha): forgets everything and sets the batching challenge (4
- *     canonical Montgomery words).
+ *     canonical Montgomery words; like every element handed in, at any 4-byte
+ *     alignment).
  *   _add_round: one commit round's `count` extensions in the order of the
  *     round's tree, matrix m rows[m] x cols[m] words in natural row order on
  *     the coset 31 <w_rows> (what _icicle_ntt_coset_lde_batch wrote), host or
@@ -614,6 +615,139 @@ TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_answer_query(tachyon_m
 TACHYON_C_EXPORT unsigned tachyon_mi355x_baby_bear_fri_opening_last_launches(
     const tachyon_mi355x_baby_bear_fri_opening* h);
 TACHYON_C_EXPORT void* tachyon_mi355x_baby_bear_fri_opening_stream(tachyon_mi355x_baby_bear_fri_opening* h);
+
+/* ---- DuplexChallenger, grinding and the opening proof in one call ------------
+ * DuplexChallenger<Poseidon2, 16, R> over BabyBear (duplex_challenger.h:33-65,
+ * challenger.h:54-127), Challenger::Grind on the GPU, the openings of a tree
+ * and the queries of an opening at many indices at once, and
+ * TwoAdicFRI::CreateOpeningProof followed by fri::Prove (two_adic_fri.h:96-219,
+ * prove.h:121-159) as one call.  Words are Montgomery words; 1 = success, 0 or
+ * NULL = refusal, and a refusal leaves the handles as they were.
+ *
+ * The challenger is host code: everything but _grind / _grind_range works
+ * without a GPU.  The permutation is the device one, bytewise.
+ *   _create(external_matrix, rate): a zero state and empty buffers; rate 1..16
+ *     words absorbed per permutation (SP1 8).  _clone: an independent copy.
+ *   _observe(values, count) (DoObserve): each word clears the output buffer and
+ *     joins the input buffer, which is duplexed at once when it holds `rate`
+ *     words.  Refused, nothing observed: a word >= p, null pointers.
+ *   _sample(out, count) (DoSample): duplexes first when there are inputs or no
+ *     outputs, then pops from the back of the output buffer (the 16 state
+ *     words).  _sample_ext(out): 4 samples, c0 first (SampleExtElement).
+ *   _sample_bits(bits, out): FromMontgomery(sample) & (2^bits - 1).  Refused
+ *     without sampling: bits above 30 (the reference requires 2^bits < p).
+ *   _check_witness(bits, witness) (CheckWitness): observes the witness, samples
+ *     the bits and returns 1 when they are 0.  The transcript advances either
+ *     way, as the reference's does; bits above 30 or a witness >= p return 0
+ *     and leave it where it was.
+ *   _state(out): 50 words: the 16 state words, the length of the input buffer
+ *     and its words in 16 slots, the length of the output buffer and its words
+ *     in 16 slots (unused slots 0).
+ *   _grind(bits, witness_out, stream) / _grind_range(bits, from, to, ...)
+ *     (Grind, challenger.h:87-122): the SMALLEST canonical w in [from, to), [0,
+ *     p) without a range, with CheckWitness(bits, w), as a Montgomery word; the
+ *     challenger is left as that CheckWitness leaves it.  The reference returns
+ *     the first hit of its first thread chunk that has one, which depends on
+ *     its thread count; on one thread it is this value.  The search runs on
+ *     the GPU in ascending chunks, one launch, one copy-back and one wait
+ *     each, and stops after the first chunk with a hit.  Refused, the
+ *     challenger unchanged: bits above 30, from >= to, to > p, null pointers, no
+ *     witness in the range (the reference CHECKs).
+ *
+ *   tachyon_mi355x_baby_bear_merkle_tree_open_batch(tree, indices, count,
+ *     rows_out, siblings_out): _open at `count` indices.  rows_out[m] receives
+ *     count x cols[m] words and siblings_out count x (num_layers - 1) digests,
+ *     query q's part what _open(indices[q]) writes.  One gather launch, one
+ *     copy per output array, one wait.
+ *   tachyon_mi355x_baby_bear_fri_opening_answer_queries(h, indices, count,
+ *     sibling_values_out, siblings_out): _answer_query at `count` indices, query
+ *     q's part in _answer_query's layout at q times its size.  One launch, two
+ *     copies, one wait.
+ *   Both refuse, writing nothing: null pointers, count 0 or above 2^16, any
+ *     index the single call refuses.
+ *
+ *   _fri_opening_prove(h, challenger, rounds, num_rounds, num_queries,
+ *     proof_of_work_bits): a round is its commit's tree, built with
+ *     TACHYON_MI355X_MERKLE_BIT_REVERSED over device-resident natural-order
+ *     extensions that it still references, and _add_round's points, num_points
+ *     and opened_values_out for the tree's matrices in its order.  The
+ *     transcript: alpha = SampleExtElement; _begin and _add_round per round
+ *     (the opened values go to the caller, who observes them afterwards, as in
+ *     the reference); per commit-phase step the root is observed and beta
+ *     sampled; final_eval is observed; the witness is ground on the GPU;
+ *     num_queries x SampleBits(log_max); one _answer_queries; one _open_batch
+ *     per round tree at index >> (log_max - the tree's log height).  Refused
+ *     with NULL, the challenger and the opening unchanged: null pointers,
+ *     num_rounds 0, num_queries 0 or above 2^16, bits above 30, a tree not
+ *     built or built without the flag, a tree or a challenger of another
+ *     external matrix than the opening's, whatever _add_round refuses.  A point
+ *     inside the coset returns NULL with the challenger restored and the
+ *     opening needing a new _begin.
+ *   _fri_proof_*: _num_commits / _commits(out) (8 words each), _final_eval(out)
+ *     (4 words), _pow_witness(out) (1 word), _num_queries / _query_index(q),
+ *     _query_steps(q, sibling_values_out, siblings_out) in _answer_query's
+ *     layout, _query_input(q, round, rows_out, siblings_out) in _open's layout,
+ *     _destroy.  Refused: null pointers, q or round out of range. */
+typedef struct tachyon_mi355x_baby_bear_duplex_challenger tachyon_mi355x_baby_bear_duplex_challenger;
+typedef struct tachyon_mi355x_baby_bear_fri_proof tachyon_mi355x_baby_bear_fri_proof;
+typedef struct {
+  tachyon_mi355x_baby_bear_merkle_tree* tree;
+  const void* const* points;
+  const size_t* num_points;
+  void* const* opened_values_out;
+} tachyon_mi355x_baby_bear_fri_round;
+TACHYON_C_EXPORT tachyon_mi355x_baby_bear_duplex_challenger* tachyon_mi355x_baby_bear_duplex_challenger_create(
+    int external_matrix, unsigned rate);
+TACHYON_C_EXPORT tachyon_mi355x_baby_bear_duplex_challenger* tachyon_mi355x_baby_bear_duplex_challenger_clone(
+    const tachyon_mi355x_baby_bear_duplex_challenger* c);
+TACHYON_C_EXPORT void tachyon_mi355x_baby_bear_duplex_challenger_destroy(
+    tachyon_mi355x_baby_bear_duplex_challenger* c);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_observe(tachyon_mi355x_baby_bear_duplex_challenger* c,
+                                                                        const uint32_t* values, size_t count);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_sample(tachyon_mi355x_baby_bear_duplex_challenger* c,
+                                                                       uint32_t* out, size_t count);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_sample_ext(
+    tachyon_mi355x_baby_bear_duplex_challenger* c, void* out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_sample_bits(
+    tachyon_mi355x_baby_bear_duplex_challenger* c, unsigned bits, uint32_t* out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_check_witness(
+    tachyon_mi355x_baby_bear_duplex_challenger* c, unsigned bits, uint32_t witness);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_state(
+    const tachyon_mi355x_baby_bear_duplex_challenger* c, uint32_t* out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_grind(tachyon_mi355x_baby_bear_duplex_challenger* c,
+                                                                      unsigned bits, uint32_t* witness_out,
+                                                                      void* stream);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_duplex_challenger_grind_range(
+    tachyon_mi355x_baby_bear_duplex_challenger* c, unsigned bits, uint64_t from, uint64_t to, uint32_t* witness_out,
+    void* stream);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_merkle_tree_open_batch(tachyon_mi355x_baby_bear_merkle_tree* tree,
+                                                                     const size_t* indices, size_t count,
+                                                                     void* const* rows_out, void* siblings_out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_opening_answer_queries(tachyon_mi355x_baby_bear_fri_opening* h,
+                                                                         const size_t* indices, size_t count,
+                                                                         void* sibling_values_out,
+                                                                         void* siblings_out);
+TACHYON_C_EXPORT tachyon_mi355x_baby_bear_fri_proof* tachyon_mi355x_baby_bear_fri_opening_prove(
+    tachyon_mi355x_baby_bear_fri_opening* h, tachyon_mi355x_baby_bear_duplex_challenger* challenger,
+    const tachyon_mi355x_baby_bear_fri_round* rounds, size_t num_rounds, size_t num_queries,
+    unsigned proof_of_work_bits);
+TACHYON_C_EXPORT void tachyon_mi355x_baby_bear_fri_proof_destroy(tachyon_mi355x_baby_bear_fri_proof* proof);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_fri_proof_num_commits(const tachyon_mi355x_baby_bear_fri_proof* proof);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_proof_commits(const tachyon_mi355x_baby_bear_fri_proof* proof,
+                                                                void* out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_proof_final_eval(const tachyon_mi355x_baby_bear_fri_proof* proof,
+                                                                   void* out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_proof_pow_witness(const tachyon_mi355x_baby_bear_fri_proof* proof,
+                                                                    uint32_t* out);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_fri_proof_num_queries(const tachyon_mi355x_baby_bear_fri_proof* proof);
+TACHYON_C_EXPORT size_t tachyon_mi355x_baby_bear_fri_proof_query_index(const tachyon_mi355x_baby_bear_fri_proof* proof,
+                                                                       size_t q);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_proof_query_steps(const tachyon_mi355x_baby_bear_fri_proof* proof,
+                                                                    size_t q, void* sibling_values_out,
+                                                                    void* siblings_out);
+TACHYON_C_EXPORT int tachyon_mi355x_baby_bear_fri_proof_query_input(const tachyon_mi355x_baby_bear_fri_proof* proof,
+                                                                    size_t q, size_t round, void* const* rows_out,
+                                                                    void* siblings_out);
 
 /* ---- communicators and library-level sharded entry points ------------------
  * One process per MI355X: a multi-process C/C++ caller (benchmark/msm/

@@ -1,9 +1,10 @@
 /* The FRI opening over BabyBear / BabyBear4 on the MI355X: a header-only C++17
  * wrapper of the tachyon_mi355x_baby_bear_fri_opening_* C-ABI with the
- * reference's names (two_adic_fri.h:96-219, prove.h).  It is
- * TwoAdicFRI::CreateOpeningProof without the challenger: the caller's
- * transcript samples alpha, observes every commit-phase root and samples the
- * beta that follows it.
+ * reference's names (two_adic_fri.h:96-219, prove.h).  FriOpening::Prove is
+ * TwoAdicFRI::CreateOpeningProof followed by fri::Prove in one call, with the
+ * transcript in a DuplexChallenger and its Grind on the GPU.  The step-by-step
+ * form stays: there the caller's transcript samples alpha, observes every
+ * commit-phase root and samples the beta that follows it.
  *
  * F is the 4-byte BabyBear element (one uint32 Montgomery word); an extension
  * element is std::array<F, 4> (c0..c3 of F[x] / (x^4 - 11)).  The matrices are
@@ -15,6 +16,7 @@
 #include <array>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -33,6 +35,83 @@ template <class F>
   static_assert(sizeof(F) == 4, "BabyBear: one uint32 Montgomery word");
   return tachyon_mi355x_baby_bear4_ops(static_cast<int>(op), a, b, out, count, stream) == 1;
 }
+
+/* DuplexChallenger<Poseidon2, 16, rate> over BabyBear (duplex_challenger.h,
+ * challenger.h) on the host, with Grind on the GPU.  Copying clones the
+ * transcript. */
+template <class F>
+class DuplexChallenger {
+ public:
+  static_assert(sizeof(F) == 4, "BabyBear: one uint32 Montgomery word");
+  using ExtF = std::array<F, 4>;
+
+  explicit DuplexChallenger(Poseidon2ExternalMatrix external = Poseidon2ExternalMatrix::kHorizen, uint32_t rate = 8)
+      : handle_(tachyon_mi355x_baby_bear_duplex_challenger_create(static_cast<int>(external), rate)) {}
+  DuplexChallenger(const DuplexChallenger& other)
+      : handle_(tachyon_mi355x_baby_bear_duplex_challenger_clone(other.handle_)) {}
+  DuplexChallenger& operator=(const DuplexChallenger& other) {
+    if (this != &other) {
+      tachyon_mi355x_baby_bear_duplex_challenger_destroy(handle_);
+      handle_ = tachyon_mi355x_baby_bear_duplex_challenger_clone(other.handle_);
+    }
+    return *this;
+  }
+  ~DuplexChallenger() { tachyon_mi355x_baby_bear_duplex_challenger_destroy(handle_); }
+
+  explicit operator bool() const { return handle_ != nullptr; }
+
+  /* false, and nothing is observed, for a value that is not below p */
+  [[nodiscard]] bool Observe(const F& value) { return ObserveWords(&value, 1); }
+  template <class Container>
+  [[nodiscard]] bool ObserveContainer(const Container& container) {
+    return ObserveWords(container.data(), container.size());
+  }
+
+  F Sample() {
+    F out{};
+    if (handle_) (void)tachyon_mi355x_baby_bear_duplex_challenger_sample(handle_, reinterpret_cast<uint32_t*>(&out), 1);
+    return out;
+  }
+  ExtF SampleExtElement() {
+    ExtF out{};
+    if (handle_) (void)tachyon_mi355x_baby_bear_duplex_challenger_sample_ext(handle_, out.data());
+    return out;
+  }
+  /* bits <= 30 (the reference requires 2^bits < p); 0 without sampling above */
+  uint32_t SampleBits(uint32_t bits) {
+    uint32_t out = 0;
+    if (handle_) (void)tachyon_mi355x_baby_bear_duplex_challenger_sample_bits(handle_, bits, &out);
+    return out;
+  }
+  [[nodiscard]] bool CheckWitness(uint32_t bits, const F& witness) {
+    uint32_t w;
+    std::memcpy(&w, &witness, sizeof w);
+    return handle_ && tachyon_mi355x_baby_bear_duplex_challenger_check_witness(handle_, bits, w) == 1;
+  }
+  /* Grind(bits) on the GPU: the smallest witness.  false (the reference
+   * CHECKs) when there is none, with the transcript unchanged. */
+  [[nodiscard]] bool Grind(uint32_t bits, F* witness, void* stream = nullptr) {
+    return handle_ && witness &&
+           tachyon_mi355x_baby_bear_duplex_challenger_grind(handle_, bits, reinterpret_cast<uint32_t*>(witness),
+                                                            stream) == 1;
+  }
+  /* Grind(bits, Range) over the canonical candidates [from, to) */
+  [[nodiscard]] bool Grind(uint32_t bits, uint32_t from, uint32_t to, F* witness, void* stream = nullptr) {
+    return handle_ && witness &&
+           tachyon_mi355x_baby_bear_duplex_challenger_grind_range(handle_, bits, from, to,
+                                                                  reinterpret_cast<uint32_t*>(witness), stream) == 1;
+  }
+
+  tachyon_mi355x_baby_bear_duplex_challenger* handle() { return handle_; }
+
+ private:
+  bool ObserveWords(const F* values, size_t count) {
+    return handle_ && tachyon_mi355x_baby_bear_duplex_challenger_observe(
+                          handle_, reinterpret_cast<const uint32_t*>(values), count) == 1;
+  }
+
+  tachyon_mi355x_baby_bear_duplex_challenger* handle_ = nullptr;
+};
 
 template <class F>
 class FriOpening {
@@ -155,6 +234,145 @@ class FriOpening {
       steps->push_back({values[i], std::vector<Digest>(siblings.begin() + at, siblings.begin() + at + count)});
       at += count;
     }
+    return true;
+  }
+
+  /* fri::AnswerQuery at every index with one launch */
+  [[nodiscard]] bool AnswerQueries(const std::vector<size_t>& indices,
+                                   std::vector<std::vector<CommitPhaseProofStep>>* steps) const {
+    if (!handle_ || !steps || num_inputs() == 0) return false;
+    const size_t commits = num_commits(), count = indices.size();
+    const uint32_t log_max = input_log_size(0);
+    size_t total = 0;
+    for (size_t i = 0; i < commits; ++i) total += log_max - i - 1;
+    std::vector<ExtF> values(count * commits + 1);
+    std::vector<Digest> siblings(count * total + 1);
+    if (tachyon_mi355x_baby_bear_fri_opening_answer_queries(handle_, indices.data(), count, values.data(),
+                                                            siblings.data()) != 1)
+      return false;
+    steps->assign(count, {});
+    for (size_t q = 0; q < count; ++q) {
+      size_t at = q * total;
+      for (size_t i = 0; i < commits; ++i) {
+        const size_t n = log_max - i - 1;
+        (*steps)[q].push_back(
+            {values[q * commits + i], std::vector<Digest>(siblings.begin() + at, siblings.begin() + at + n)});
+        at += n;
+      }
+    }
+    return true;
+  }
+
+  /* The reference's proof types (fri_proof.h, two_adic_fri.h). */
+  struct BatchOpening {
+    std::vector<std::vector<F>> opened_values;  /* the opened row per matrix of the round */
+    std::vector<Digest> opening_proof;
+  };
+  struct QueryProof {
+    std::vector<BatchOpening> input_proof;  /* one per round */
+    std::vector<CommitPhaseProofStep> commit_phase_openings;
+  };
+  struct FRIProof {
+    std::vector<Digest> commit_phase_commits;
+    std::vector<QueryProof> query_proofs;
+    ExtF final_eval{};
+    F pow_witness{};
+    std::vector<size_t> query_indices;  /* what the verifier samples again */
+  };
+  /* One commit round: the tree Commit() returned and the opening points of
+   * each of its matrices. */
+  struct Round {
+    FieldMerkleTree<F>* tree = nullptr;
+    std::vector<std::vector<ExtF>> points;
+  };
+
+  /* TwoAdicFRI::CreateOpeningProof followed by fri::Prove in one call, the
+   * transcript in `challenger` (which has observed what precedes alpha).  The
+   * opened values are returned for the caller to observe afterwards, as in the
+   * reference.  false on refusal (see tachyon_mi355x.h), with the challenger
+   * as it was. */
+  [[nodiscard]] bool Prove(DuplexChallenger<F>& challenger, const std::vector<Round>& rounds, size_t num_queries,
+                           uint32_t proof_of_work_bits, FRIProof* proof,
+                           std::vector<OpenedValuesForRound>* opened_values) {
+    if (!handle_ || !challenger || !proof || !opened_values || rounds.empty()) return false;
+    const size_t nr = rounds.size();
+    std::vector<tachyon_mi355x_baby_bear_fri_round> recs(nr);
+    std::vector<std::vector<const void*>> pts(nr);
+    std::vector<std::vector<size_t>> num(nr);
+    std::vector<std::vector<void*>> outs(nr);
+    std::vector<std::vector<std::vector<ExtF>>> flat(nr);
+    for (size_t r = 0; r < nr; ++r) {
+      const Round& round = rounds[r];
+      if (!round.tree || round.points.size() != round.tree->leaves().size()) return false;
+      const auto& leaves = round.tree->leaves();
+      const size_t n = leaves.size();
+      pts[r].resize(n), num[r].resize(n), outs[r].resize(n), flat[r].resize(n);
+      for (size_t m = 0; m < n; ++m) {
+        num[r][m] = round.points[m].size();
+        pts[r][m] = round.points[m].data();
+        flat[r][m].resize(num[r][m] * leaves[m].cols);
+        outs[r][m] = flat[r][m].data();
+      }
+      recs[r] = {round.tree->handle(), pts[r].data(), num[r].data(), outs[r].data()};
+    }
+    tachyon_mi355x_baby_bear_fri_proof* p = tachyon_mi355x_baby_bear_fri_opening_prove(
+        handle_, challenger.handle(), recs.data(), nr, num_queries, proof_of_work_bits);
+    if (!p) return false;
+
+    std::vector<OpenedValuesForRound> opened(nr);
+    for (size_t r = 0; r < nr; ++r) {
+      const auto& leaves = rounds[r].tree->leaves();
+      opened[r].resize(leaves.size());
+      for (size_t m = 0; m < leaves.size(); ++m)
+        for (size_t k = 0; k < num[r][m]; ++k)
+          opened[r][m].emplace_back(flat[r][m].begin() + k * leaves[m].cols,
+                                    flat[r][m].begin() + (k + 1) * leaves[m].cols);
+    }
+    FRIProof result;
+    const size_t commits = tachyon_mi355x_baby_bear_fri_proof_num_commits(p);
+    const uint32_t log_max = input_log_size(0);
+    result.commit_phase_commits.resize(commits);
+    Digest unused;
+    bool ok = tachyon_mi355x_baby_bear_fri_proof_commits(
+                  p, commits ? result.commit_phase_commits.data()->data() : unused.data()) == 1 &&
+              tachyon_mi355x_baby_bear_fri_proof_final_eval(p, result.final_eval.data()) == 1 &&
+              tachyon_mi355x_baby_bear_fri_proof_pow_witness(p, reinterpret_cast<uint32_t*>(&result.pow_witness)) == 1;
+    size_t total = 0;
+    for (size_t i = 0; i < commits; ++i) total += log_max - i - 1;
+    const size_t queries = tachyon_mi355x_baby_bear_fri_proof_num_queries(p);
+    result.query_proofs.resize(queries);
+    std::vector<ExtF> values(commits + 1);
+    std::vector<Digest> siblings(total + 1);
+    for (size_t q = 0; ok && q < queries; ++q) {
+      QueryProof& qp = result.query_proofs[q];
+      result.query_indices.push_back(tachyon_mi355x_baby_bear_fri_proof_query_index(p, q));
+      ok = tachyon_mi355x_baby_bear_fri_proof_query_steps(p, q, values.data(), siblings.data()) == 1;
+      size_t at = 0;
+      for (size_t i = 0; ok && i < commits; ++i) {
+        const size_t n = log_max - i - 1;
+        qp.commit_phase_openings.push_back(
+            {values[i], std::vector<Digest>(siblings.begin() + at, siblings.begin() + at + n)});
+        at += n;
+      }
+      for (size_t r = 0; ok && r < nr; ++r) {
+        const auto& leaves = rounds[r].tree->leaves();
+        BatchOpening opening;
+        std::vector<void*> rows(leaves.size());
+        for (size_t m = 0; m < leaves.size(); ++m) {
+          opening.opened_values.emplace_back(leaves[m].cols);
+          rows[m] = opening.opened_values.back().data();
+        }
+        const size_t layers = tachyon_mi355x_baby_bear_merkle_tree_num_layers(rounds[r].tree->handle());
+        opening.opening_proof.resize(layers - 1);
+        ok = tachyon_mi355x_baby_bear_fri_proof_query_input(
+                 p, q, r, rows.data(), layers > 1 ? opening.opening_proof.data()->data() : unused.data()) == 1;
+        qp.input_proof.push_back(std::move(opening));
+      }
+    }
+    tachyon_mi355x_baby_bear_fri_proof_destroy(p);
+    if (!ok) return false;
+    *proof = std::move(result);
+    *opened_values = std::move(opened);
     return true;
   }
 

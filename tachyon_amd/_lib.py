@@ -36,6 +36,14 @@ class MsmShard(ctypes.Structure):
     _fields_ = [("start", ctypes.c_size_t), ("count", ctypes.c_size_t), ("point_groups", ctypes.c_uint),
                 ("window_groups", ctypes.c_uint), ("window_bits", ctypes.c_uint), ("w_begin", ctypes.c_uint),
                 ("w_end", ctypes.c_uint)]
+
+
+class FriRound(ctypes.Structure):
+    """tachyon_mi355x_baby_bear_fri_round: one commit round of _fri_opening_prove."""
+    _fields_ = [("tree", ctypes.c_void_p), ("points", ctypes.POINTER(ctypes.c_void_p)),
+                ("num_points", ctypes.POINTER(ctypes.c_size_t)), ("opened_values_out", ctypes.POINTER(ctypes.c_void_p))]
+
+
 SIGNATURES = [
     # reference C-ABI: MSM
     ("tachyon_bn254_g1_init", None, []),
@@ -241,6 +249,33 @@ SIGNATURES = [
     ("tachyon_mi355x_baby_bear_fri_opening_answer_query", i32, [vp, sz, vp, vp]),
     ("tachyon_mi355x_baby_bear_fri_opening_last_launches", ctypes.c_uint, [vp]),
     ("tachyon_mi355x_baby_bear_fri_opening_stream", vp, [vp]),
+    # DuplexChallenger, grinding, batched openings and the opening proof in one call
+    ("tachyon_mi355x_baby_bear_duplex_challenger_create", vp, [i32, ctypes.c_uint]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_clone", vp, [vp]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_destroy", None, [vp]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_observe", i32, [vp, vp, sz]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_sample", i32, [vp, vp, sz]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_sample_ext", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_sample_bits", i32, [vp, ctypes.c_uint,
+                                                                     ctypes.POINTER(ctypes.c_uint32)]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_check_witness", i32, [vp, ctypes.c_uint, ctypes.c_uint32]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_state", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_grind", i32, [vp, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32), vp]),
+    ("tachyon_mi355x_baby_bear_duplex_challenger_grind_range", i32, [vp, ctypes.c_uint, u64, u64,
+                                                                     ctypes.POINTER(ctypes.c_uint32), vp]),
+    ("tachyon_mi355x_baby_bear_merkle_tree_open_batch", i32, [vp, ctypes.POINTER(ctypes.c_size_t), sz,
+                                                              ctypes.POINTER(ctypes.c_void_p), vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_answer_queries", i32, [vp, ctypes.POINTER(ctypes.c_size_t), sz, vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_opening_prove", vp, [vp, vp, vp, sz, sz, ctypes.c_uint]),
+    ("tachyon_mi355x_baby_bear_fri_proof_destroy", None, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_proof_num_commits", sz, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_proof_commits", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_proof_final_eval", i32, [vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_proof_pow_witness", i32, [vp, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tachyon_mi355x_baby_bear_fri_proof_num_queries", sz, [vp]),
+    ("tachyon_mi355x_baby_bear_fri_proof_query_index", sz, [vp, sz]),
+    ("tachyon_mi355x_baby_bear_fri_proof_query_steps", i32, [vp, sz, vp, vp]),
+    ("tachyon_mi355x_baby_bear_fri_proof_query_input", i32, [vp, sz, sz, ctypes.POINTER(ctypes.c_void_p), vp]),
     # communicators and library-level sharded entry points
     ("tachyon_mi355x_comm_unique_id", i32, [vp, sz]),
     ("tachyon_mi355x_comm_init_rccl", vp, [vp, i32, i32]),

@@ -3,19 +3,25 @@
 // and phase rules live in fri_validate.h.
 #include "../../../include/tachyon_mi355x.h"
 
+#include <cstring>
 #include <memory>
 
 #include "../common/hip_util.h"
 #include "../fri/fri_bb.h"
+#include "capi_handles.h"
 #include "fri_validate.h"
 #include "merkle_tree_validate.h"
 
 using namespace tachyon_amd;
 using fri::Fp4;
 
-struct tachyon_mi355x_baby_bear_fri_opening {
-  std::unique_ptr<fri::FriOpening> fri;
-};
+// A caller's element is 4 words at any 4-byte alignment (a std::array<F, 4> on
+// the stack); Fp4 is alignas(16), so it is copied, never reinterpreted.
+static Fp4 load_ext(const void* p) {
+  Fp4 v;
+  memcpy(v.c, p, sizeof v.c);
+  return v;
+}
 
 extern "C" {
 
@@ -71,7 +77,7 @@ void tachyon_mi355x_baby_bear_fri_opening_destroy(tachyon_mi355x_baby_bear_fri_o
 int tachyon_mi355x_baby_bear_fri_opening_begin(tachyon_mi355x_baby_bear_fri_opening* h, const void* alpha) {
   if (!h || !alpha) return 0;
   try {
-    return h->fri->begin(*static_cast<const Fp4*>(alpha)) ? 1 : 0;
+    return h->fri->begin(load_ext(alpha)) ? 1 : 0;
   } catch (...) {
     return 0;
   }
@@ -123,7 +129,7 @@ int tachyon_mi355x_baby_bear_fri_opening_commit(tachyon_mi355x_baby_bear_fri_ope
 int tachyon_mi355x_baby_bear_fri_opening_fold(tachyon_mi355x_baby_bear_fri_opening* h, const void* beta) {
   if (!h || !beta) return 0;
   try {
-    return h->fri->fold(*static_cast<const Fp4*>(beta)) ? 1 : 0;
+    return h->fri->fold(load_ext(beta)) ? 1 : 0;
   } catch (...) {
     return 0;
   }

@@ -7,15 +7,12 @@
 
 #include "../common/hip_util.h"
 #include "../hash/merkle_bb.h"
+#include "capi_handles.h"
 #include "merkle_tree_validate.h"
 
 using namespace tachyon_amd;
 
 static_assert(TACHYON_MI355X_MERKLE_BIT_REVERSED == merkle_tree::kFlagBitReversed);
-
-struct tachyon_mi355x_baby_bear_merkle_tree {
-  std::unique_ptr<hash::BbMerkleTree> tree;
-};
 
 extern "C" {
 

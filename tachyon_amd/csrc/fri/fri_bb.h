@@ -3,7 +3,9 @@
 // openings of every committed matrix, the commit phase (a FieldMerkleTree per
 // fold step over the folded vector viewed as size/2 x 8 words) and the queries.
 // alpha and each beta are inputs; each commit-phase root is handed back before
-// the next beta is needed.
+// the next beta is needed.  prove() runs the same steps with the transcript in
+// a DuplexChallenger (challenger_bb.h), grinds on the GPU (grind_bb.h) and
+// answers all queries at once (fri_prove_bb.hip).
 //
 // The matrices are the natural-order extensions Commit left on the coset
 // 31 <w_n>.  The reference indexes everything in bit-reversed row order:
@@ -34,6 +36,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -41,6 +44,7 @@
 #include "../common/hip_util.h"
 #include "../field/bb31x4.h"
 #include "../hash/merkle_bb.h"
+#include "challenger_bb.h"
 
 namespace tachyon_amd::fri {
 
@@ -48,11 +52,49 @@ using bb31x4::Fp4;
 
 inline constexpr unsigned kPointGroup = 8;     // points interpolated per read of the block
 
+// The element at p[i] of a caller's array of 4-word elements, which is aligned
+// to 4 bytes only (Fp4 is alignas(16)): copied, never reinterpreted.
+inline Fp4 load_ext(const void* p, size_t i) {
+  Fp4 v;
+  memcpy(v.c, static_cast<const uint32_t*>(p) + 4 * i, sizeof v.c);
+  return v;
+}
+
 enum Bb4Op : int { kBb4Add = 0, kBb4Sub = 1, kBb4Mul = 2, kBb4Square = 3, kBb4Inverse = 4, kBb4NumOps = 5 };
 
 // out[i] = a[i] op b[i] on `count` elements of device memory (b unused by
 // square and inverse), enqueued on `stream`
 void bb4_ops(int op, const Fp4* d_a, const Fp4* d_b, Fp4* d_out, size_t count, hipStream_t stream);
+
+// One commit round of FriOpening::prove: the round's tree (built with
+// kFlagBitReversed over the natural-order extensions, which it still
+// references) and add_round's points and outputs for the tree's matrices.
+struct ProveRound {
+  hash::BbMerkleTree* tree;
+  const void* const* points;
+  const size_t* num_points;
+  void* const* opened_values_out;
+};
+
+// fri::FRIProof plus the input openings of TwoAdicFRI::CreateOpeningProof, in
+// the layouts of answer_queries and BbMerkleTree::open_batch.
+struct Proof {
+  struct RoundOpenings {
+    std::vector<size_t> cols;                 // per matrix
+    std::vector<std::vector<uint32_t>> rows;  // per matrix: num_queries x cols words
+    size_t num_siblings = 0;                  // digests per query
+    std::vector<uint32_t> siblings;           // num_queries x num_siblings x 8 words
+  };
+  std::vector<uint32_t> commits;  // 8 words per commit-phase root
+  Fp4 final_eval{};
+  uint32_t pow_witness = 0;
+  unsigned log_max = 0;
+  std::vector<size_t> indices;
+  std::vector<uint32_t> sibling_values;  // num_queries x num_commits x 4 words
+  std::vector<uint32_t> siblings;        // num_queries x query_total_siblings x 8 words
+  std::vector<RoundOpenings> rounds;
+  size_t num_commits() const { return commits.size() / 8; }
+};
 
 class FriOpening {
  public:
@@ -82,7 +124,22 @@ class FriOpening {
   size_t num_commits() const { return num_commits_; }
   bool final_poly(void* out);  // waits
   bool answer_query(size_t index, void* sibling_values_out, void* siblings_out);  // waits once
+  // answer_query at `count` indices (fri_prove_bb.hip), query q's part in
+  // answer_query's layout at q times its size.  One launch, two copies, one
+  // wait.  False, with nothing written, for a null pointer, count 0 or above
+  // kMaxQueries, or an index answer_query refuses.
+  static constexpr size_t kMaxQueries = size_t(1) << 16;
+  bool answer_queries(const size_t* indices, size_t count, void* sibling_values_out, void* siblings_out);
 
+  // CreateOpeningProof followed by fri::Prove with the transcript in
+  // `challenger` (fri_prove_bb.hip); see tachyon_mi355x_baby_bear_fri_opening_prove.
+  // False with *out untouched on refusal; the challenger is then as it was, and
+  // so is this opening unless a point lay inside the coset.
+  bool prove(DuplexChallenger& challenger, const ProveRound* rounds, size_t num_rounds, size_t num_queries,
+             unsigned proof_of_work_bits, Proof* out);
+
+  unsigned log_blowup() const { return log_blowup_; }
+  int external() const { return external_; }
   const Phase& phase() const { return phase_; }
   unsigned last_launches() const { return launches_; }
   hipStream_t stream() const { return stream_; }
@@ -123,6 +180,8 @@ class FriOpening {
   std::vector<std::unique_ptr<hash::BbMerkleTree>> trees_;  // trees_[i] over folded(i)
   size_t num_commits_ = 0;
   DeviceBuffer query_;  // a query's gathered answer
+  DeviceBuffer queries_;  // answer_queries: the indices, then the gathered answers
+  DeviceBuffer grind_;    // prove: the grind's device word
 };
 
 }  // namespace tachyon_amd::fri

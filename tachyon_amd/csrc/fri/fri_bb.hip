@@ -410,7 +410,7 @@ bool FriOpening::add_round(const void* const* ldes, const size_t* rows, const si
   for (size_t m = 0; m < count; ++m) {
     for (size_t p = 0; p < num_points[m]; ++p)
       for (int k = 0; k < 4; ++k)
-        if (static_cast<const Fp4*>(points[m])[p].c[k] >= bb31::kP) return false;
+        if (load_ext(points[m], p).c[k] >= bb31::kP) return false;
     total_points += num_points[m];
     total_ys += num_points[m] * cols[m];
     max_cols = std::max(max_cols, cols[m]);
@@ -454,7 +454,7 @@ bool FriOpening::add_round(const void* const* ldes, const size_t* rows, const si
     const uint32_t denom_inv = bb31::inverse(bb31::mul(mm, bb31::pow(g, (size_t(1) << log_m) - 1)));
     const uint32_t gm = bb31::pow(g, size_t(1) << log_m);
     for (size_t p = 0; p < num_points[m]; ++p, ++at) {
-      const Fp4 z = static_cast<const Fp4*>(points[m])[p];
+      const Fp4 z = load_ext(points[m], p);
       PointDev& pt = host_pts[at];
       memset(&pt, 0, sizeof pt);
       pt.inv = inv_denoms(z, log_n);

@@ -58,6 +58,21 @@ class BbMerkleTree {
   // past its height; siblings_out: (num_layers - 1) digests.  False for
   // index >= layer_size(0).
   bool open(size_t index, void* const* rows_out, void* siblings_out);
+  // open() at `count` indices (merkle_open_bb.hip): rows_out[m] receives count
+  // rows of cols[m] words, siblings_out count * (num_layers - 1) digests, query
+  // q's part what open(indices[q]) writes.  One gather launch, one copy per
+  // output array, one wait.  False, with nothing written, for a null pointer,
+  // count 0 or above kMaxBatch, or an index >= layer_size(0).
+  static constexpr size_t kMaxBatch = size_t(1) << 16;
+  bool open_batch(const size_t* indices, size_t count, void* const* rows_out, void* siblings_out);
+
+  // the last build's arguments, the caller's order (device pointers)
+  int external() const { return external_; }
+  unsigned flags() const { return flags_; }
+  unsigned log_max() const { return plan_.log_max; }
+  const void* matrix(size_t m) const { return m < mats_.size() ? mats_[m] : nullptr; }
+  size_t matrix_rows(size_t m) const { return m < rows_.size() ? rows_[m] : 0; }
+  size_t matrix_cols(size_t m) const { return m < cols_.size() ? cols_[m] : 0; }
 
  private:
   int external_;
@@ -70,6 +85,7 @@ class BbMerkleTree {
   std::vector<std::unique_ptr<DeviceBuffer>> uploads_;  // host matrices' device copies
   DeviceBuffer layers_;                // the layers, then the injected hashes of levels >= 1
   unsigned launches_ = 0;
+  DeviceBuffer batch_;                 // open_batch: indices and matrix records in, the gathered answer out
 };
 
 }  // namespace tachyon_amd::hash

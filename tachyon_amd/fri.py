@@ -2,11 +2,13 @@
 tachyon_mi355x_baby_bear_fri_opening_*): TwoAdicFRI::CreateOpeningProof without
 its challenger.  A BabyBear4 element is 16 bytes, 4 little-endian Montgomery
 words c0..c3 of F[x] / (x^4 - 11); a digest is 8 words.  The caller's transcript
-samples alpha and every beta.  Every call returns True / False (or None in place
+samples alpha and every beta, or DuplexChallenger (the library's, with Grind on
+the GPU) does in FriOpening.prove(), which is CreateOpeningProof followed by
+fri::Prove in one call.  Every call returns True / False (or None in place
 of data) on a refusal; only a misuse of this wrapper raises."""
 import ctypes
 
-from ._lib import lib
+from ._lib import FriRound, lib
 from .poseidon2 import DIGEST_BYTES, _external_id
 
 EXT_BYTES = 16
@@ -188,6 +190,63 @@ class FriOpening:
             at += c
         return out
 
+    def answer_queries(self, indices):
+        """answer_query() at every index with one launch: a list of
+        answer_query()'s results in the indices' order, or None."""
+        count = len(indices)
+        if self.num_inputs == 0 or any(i < 0 for i in indices):
+            return None
+        log_max, commits = self.input_log_size(0), self.num_commits
+        counts = [log_max - i - 1 for i in range(commits)]
+        total = sum(counts)
+        vals = ctypes.create_string_buffer(max(1, count * commits * EXT_BYTES))
+        sibs = ctypes.create_string_buffer(max(1, count * total * DIGEST_BYTES))
+        idx = (ctypes.c_size_t * max(1, count))(*indices)
+        if lib().tachyon_mi355x_baby_bear_fri_opening_answer_queries(self._h, idx, count, vals, sibs) != 1:
+            return None
+        return [_split_steps(vals.raw[q * commits * EXT_BYTES:(q + 1) * commits * EXT_BYTES],
+                             sibs.raw[q * total * DIGEST_BYTES:(q + 1) * total * DIGEST_BYTES], counts)
+                for q in range(count)]
+
+    def prove(self, challenger, rounds, num_queries: int, proof_of_work_bits: int):
+        """CreateOpeningProof followed by fri::Prove with the transcript in
+        `challenger`.  rounds: (FieldMerkleTree, points) per commit round, the
+        tree built bit-reversed over device-resident natural-order extensions,
+        points per matrix of the tree a list of 16-byte opening points.  Returns
+        (FriProof, the opened values per round as add_round_ptr returns them),
+        or None when refused."""
+        n = len(rounds)
+        recs = (FriRound * max(1, n))()
+        keep, outs = [], []
+        for r, (tree, points) in enumerate(rounds):
+            cols = tree._cols
+            if len(points) != len(cols):
+                raise ValueError("one list of points per matrix of the round's tree")
+            m = len(cols)
+            pbufs = [ctypes.create_string_buffer(b"".join(bytes(_ext(z).raw) for z in ps), max(1, len(ps) * EXT_BYTES))
+                     for ps in points]
+            obufs = [ctypes.create_string_buffer(max(1, len(ps) * c * EXT_BYTES)) for ps, c in zip(points, cols)]
+            pptrs = (ctypes.c_void_p * max(1, m))(*[ctypes.addressof(b) for b in pbufs])
+            nps = (ctypes.c_size_t * max(1, m))(*[len(ps) for ps in points])
+            optrs = (ctypes.c_void_p * max(1, m))(*[ctypes.addressof(b) for b in obufs])
+            recs[r] = FriRound(tree._h, pptrs, nps, optrs)
+            keep.append((pbufs, pptrs, nps, optrs))
+            outs.append(obufs)
+        h = lib().tachyon_mi355x_baby_bear_fri_opening_prove(self._h, challenger._h, recs if n else None, n, num_queries,
+                                                             proof_of_work_bits)
+        if not h:
+            return None
+        opened = []
+        for (tree, points), obufs in zip(rounds, outs):
+            per_round = []
+            for ps, c, b in zip(points, tree._cols, obufs):
+                w = c * EXT_BYTES
+                per_round.append([b.raw[p * w:(p + 1) * w] for p in range(len(ps))])
+            opened.append(per_round)
+        proof = FriProof(h, self.input_log_size(0), [list(tree._cols) for tree, _ in rounds],
+                         [tree.num_layers - 1 for tree, _ in rounds])
+        return proof, opened
+
     @property
     def last_launches(self) -> int:
         return lib().tachyon_mi355x_baby_bear_fri_opening_last_launches(self._h)
@@ -195,3 +254,172 @@ class FriOpening:
     @property
     def stream(self) -> int:
         return lib().tachyon_mi355x_baby_bear_fri_opening_stream(self._h)
+
+
+def _split_steps(vals: bytes, sibs: bytes, counts):
+    """answer_query's result from one query's sibling values and digests"""
+    out, at = [], 0
+    for i, c in enumerate(counts):
+        out.append((vals[i * EXT_BYTES:(i + 1) * EXT_BYTES],
+                    [sibs[(at + k) * DIGEST_BYTES:(at + k + 1) * DIGEST_BYTES] for k in range(c)]))
+        at += c
+    return out
+
+
+class FriProof:
+    """fri::FRIProof and the input openings, as FriOpening.prove() returns them:
+    commit_phase_commits, final_eval, pow_witness, and per query its index, its
+    commit-phase steps (answer_query's form) and its input openings per round
+    (FieldMerkleTree.open's form)."""
+
+    def __init__(self, handle, log_max, cols_by_round, siblings_by_round):
+        self._h, self._log_max = handle, log_max
+        self._cols, self._nsib = cols_by_round, siblings_by_round
+
+    def close(self):
+        if self._h:
+            lib().tachyon_mi355x_baby_bear_fri_proof_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def num_commits(self) -> int:
+        return lib().tachyon_mi355x_baby_bear_fri_proof_num_commits(self._h)
+
+    @property
+    def commit_phase_commits(self):
+        n = self.num_commits
+        buf = ctypes.create_string_buffer(max(1, n * DIGEST_BYTES))
+        if lib().tachyon_mi355x_baby_bear_fri_proof_commits(self._h, buf) != 1:
+            return None
+        return [buf.raw[k * DIGEST_BYTES:(k + 1) * DIGEST_BYTES] for k in range(n)]
+
+    @property
+    def final_eval(self):
+        buf = ctypes.create_string_buffer(EXT_BYTES)
+        return buf.raw if lib().tachyon_mi355x_baby_bear_fri_proof_final_eval(self._h, buf) == 1 else None
+
+    @property
+    def pow_witness(self):
+        """the witness as a Montgomery word"""
+        w = ctypes.c_uint32()
+        return w.value if lib().tachyon_mi355x_baby_bear_fri_proof_pow_witness(self._h, ctypes.byref(w)) == 1 else None
+
+    @property
+    def num_queries(self) -> int:
+        return lib().tachyon_mi355x_baby_bear_fri_proof_num_queries(self._h)
+
+    def query_index(self, q: int) -> int:
+        return lib().tachyon_mi355x_baby_bear_fri_proof_query_index(self._h, q)
+
+    def query_steps(self, q: int):
+        """commit_phase_openings of query q, or None"""
+        commits = self.num_commits
+        counts = [self._log_max - i - 1 for i in range(commits)]
+        vals = ctypes.create_string_buffer(max(1, commits * EXT_BYTES))
+        sibs = ctypes.create_string_buffer(max(1, sum(counts) * DIGEST_BYTES))
+        if q < 0 or lib().tachyon_mi355x_baby_bear_fri_proof_query_steps(self._h, q, vals, sibs) != 1:
+            return None
+        return _split_steps(vals.raw, sibs.raw, counts)
+
+    def query_input(self, q: int, round_index: int):
+        """input_proof of query q for one round: (rows per matrix, siblings), or None"""
+        if q < 0 or not 0 <= round_index < len(self._cols):
+            return None
+        cols, n = self._cols[round_index], self._nsib[round_index]
+        rows = [ctypes.create_string_buffer(max(1, c * 4)) for c in cols]
+        ptrs = (ctypes.c_void_p * max(1, len(rows)))(*[ctypes.addressof(r) for r in rows])
+        sib = ctypes.create_string_buffer(max(1, n * DIGEST_BYTES))
+        if lib().tachyon_mi355x_baby_bear_fri_proof_query_input(self._h, q, round_index, ptrs, sib) != 1:
+            return None
+        return ([r.raw[:c * 4] for r, c in zip(rows, cols)],
+                [sib.raw[k * DIGEST_BYTES:(k + 1) * DIGEST_BYTES] for k in range(n)])
+
+
+class DuplexChallenger:
+    """DuplexChallenger<Poseidon2, 16, rate> over BabyBear on the host, with
+    Grind on the GPU.  Words are 4-byte little-endian Montgomery words, as
+    everywhere in this package."""
+
+    def __init__(self, external="horizen", rate: int = 8, _handle=None):
+        self._h = _handle or lib().tachyon_mi355x_baby_bear_duplex_challenger_create(_external_id(external), rate)
+        if not self._h:
+            raise RuntimeError("DuplexChallenger creation failed")
+
+    def clone(self):
+        h = lib().tachyon_mi355x_baby_bear_duplex_challenger_clone(self._h)
+        if not h:
+            raise RuntimeError("DuplexChallenger clone failed")
+        return DuplexChallenger(_handle=h)
+
+    def close(self):
+        if self._h:
+            lib().tachyon_mi355x_baby_bear_duplex_challenger_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def observe(self, values: bytes) -> bool:
+        """False, with nothing observed, when a word is not below p"""
+        data = bytes(values)
+        if len(data) % 4:
+            raise ValueError("values are words of 4 bytes")
+        buf = ctypes.create_string_buffer(data, max(1, len(data)))
+        return lib().tachyon_mi355x_baby_bear_duplex_challenger_observe(self._h, buf, len(data) // 4) == 1
+
+    def sample(self, count: int = 1) -> bytes:
+        buf = ctypes.create_string_buffer(max(1, 4 * count))
+        if lib().tachyon_mi355x_baby_bear_duplex_challenger_sample(self._h, buf, count) != 1:
+            return None
+        return buf.raw[:4 * count]
+
+    def sample_ext(self) -> bytes:
+        buf = ctypes.create_string_buffer(EXT_BYTES)
+        return buf.raw if lib().tachyon_mi355x_baby_bear_duplex_challenger_sample_ext(self._h, buf) == 1 else None
+
+    def sample_bits(self, bits: int):
+        """the low bits of the next sample's canonical value, or None above 30 bits"""
+        out = ctypes.c_uint32()
+        if bits < 0 or lib().tachyon_mi355x_baby_bear_duplex_challenger_sample_bits(self._h, bits,
+                                                                                    ctypes.byref(out)) != 1:
+            return None
+        return out.value
+
+    def check_witness(self, bits: int, witness: int) -> bool:
+        """witness: a Montgomery word"""
+        if bits < 0 or not 0 <= witness < 1 << 32:
+            return False
+        return lib().tachyon_mi355x_baby_bear_duplex_challenger_check_witness(self._h, bits, witness) == 1
+
+    def state(self):
+        """(the 16 state words, the input buffer, the output buffer) as bytes"""
+        buf = (ctypes.c_uint32 * 50)()
+        if lib().tachyon_mi355x_baby_bear_duplex_challenger_state(self._h, buf) != 1:
+            return None
+        raw = bytes(buf)
+        return raw[:64], raw[68:68 + 4 * buf[16]], raw[136:136 + 4 * buf[33]]
+
+    def grind(self, bits: int, stream: int = None):
+        """Grind(bits) on the GPU: the smallest witness as a Montgomery word, or None"""
+        out = ctypes.c_uint32()
+        if bits < 0 or lib().tachyon_mi355x_baby_bear_duplex_challenger_grind(self._h, bits, ctypes.byref(out),
+                                                                              stream) != 1:
+            return None
+        return out.value
+
+    def grind_range(self, bits: int, begin: int, end: int, stream: int = None):
+        """Grind(bits, Range) over the canonical candidates [begin, end)"""
+        out = ctypes.c_uint32()
+        if bits < 0 or begin < 0 or end < 0 or lib().tachyon_mi355x_baby_bear_duplex_challenger_grind_range(
+                self._h, bits, begin, end, ctypes.byref(out), stream) != 1:
+            return None
+        return out.value

@@ -135,6 +135,25 @@ class FieldMerkleTree:
         return ([r.raw[:c * WORD] for r, c in zip(rows, self._cols)],
                 [sib.raw[k * DIGEST_BYTES:(k + 1) * DIGEST_BYTES] for k in range(n - 1)])
 
+    def open_batch(self, indices):
+        """open() at every index with one gather launch: a list of open()'s
+        results in the indices' order, or None."""
+        n, count = self.num_layers, len(indices)
+        if n == 0 or any(i < 0 for i in indices):
+            return None
+        rows = [ctypes.create_string_buffer(max(1, count * c * WORD)) for c in self._cols]
+        ptrs = (ctypes.c_void_p * max(1, len(rows)))(*[ctypes.addressof(r) for r in rows])
+        sib = ctypes.create_string_buffer(max(1, count * (n - 1) * DIGEST_BYTES))
+        idx = (ctypes.c_size_t * max(1, count))(*indices)
+        if lib().tachyon_mi355x_baby_bear_merkle_tree_open_batch(self._h, idx, count, ptrs, sib) != 1:
+            return None
+        raws, sraw, out = [r.raw for r in rows], sib.raw, []
+        for q in range(count):
+            base = q * (n - 1)
+            out.append(([r[q * c * WORD:(q + 1) * c * WORD] for r, c in zip(raws, self._cols)],
+                        [sraw[(base + k) * DIGEST_BYTES:(base + k + 1) * DIGEST_BYTES] for k in range(n - 1)]))
+        return out
+
     @property
     def last_launches(self) -> int:
         return lib().tachyon_mi355x_baby_bear_merkle_tree_last_launches(self._h)
