@@ -152,27 +152,18 @@ class FriOpening {
                                     OpenedValuesForRound* opened_values) {
     if (!handle_ || !opened_values || points.size() != ldes.size()) return false;
     const size_t n = ldes.size();
-    std::vector<const void*> data(n), pts(n);
-    std::vector<void*> out(n);
-    std::vector<size_t> rows(n), cols(n), num(n);
-    std::vector<std::vector<ExtF>> flat(n);
+    std::vector<const void*> data(n);
+    std::vector<size_t> rows(n), cols(n);
     for (size_t m = 0; m < n; ++m) {
       data[m] = ldes[m].data;
       rows[m] = ldes[m].rows;
       cols[m] = ldes[m].cols;
-      num[m] = points[m].size();
-      pts[m] = points[m].data();
-      flat[m].resize(points[m].size() * ldes[m].cols);
-      out[m] = flat[m].data();
     }
-    if (tachyon_mi355x_baby_bear_fri_opening_add_round(handle_, data.data(), rows.data(), cols.data(), n, pts.data(),
-                                                       num.data(), out.data()) != 1)
+    PointArgs args(points, cols);
+    if (tachyon_mi355x_baby_bear_fri_opening_add_round(handle_, data.data(), rows.data(), cols.data(), n,
+                                                       args.points.data(), args.num.data(), args.out.data()) != 1)
       return false;
-    OpenedValuesForRound result(n);
-    for (size_t m = 0; m < n; ++m)
-      for (size_t p = 0; p < points[m].size(); ++p)
-        result[m].emplace_back(flat[m].begin() + p * cols[m], flat[m].begin() + (p + 1) * cols[m]);
-    *opened_values = std::move(result);
+    *opened_values = args.Opened();
     return true;
   }
 
@@ -221,19 +212,11 @@ class FriOpening {
     if (!handle_ || !steps || num_inputs() == 0) return false;
     const size_t commits = num_commits();
     const uint32_t log_max = input_log_size(0);
-    size_t total = 0;
-    for (size_t i = 0; i < commits; ++i) total += log_max - i - 1;
     std::vector<ExtF> values(commits + 1);
-    std::vector<Digest> siblings(total + 1);
+    std::vector<Digest> siblings(TotalSiblings(log_max, commits) + 1);
     if (tachyon_mi355x_baby_bear_fri_opening_answer_query(handle_, index, values.data(), siblings.data()) != 1)
       return false;
-    steps->clear();
-    size_t at = 0;
-    for (size_t i = 0; i < commits; ++i) {
-      const size_t count = log_max - i - 1;
-      steps->push_back({values[i], std::vector<Digest>(siblings.begin() + at, siblings.begin() + at + count)});
-      at += count;
-    }
+    *steps = SplitSteps(values.data(), siblings.data(), log_max, commits);
     return true;
   }
 
@@ -243,23 +226,15 @@ class FriOpening {
     if (!handle_ || !steps || num_inputs() == 0) return false;
     const size_t commits = num_commits(), count = indices.size();
     const uint32_t log_max = input_log_size(0);
-    size_t total = 0;
-    for (size_t i = 0; i < commits; ++i) total += log_max - i - 1;
+    const size_t total = TotalSiblings(log_max, commits);
     std::vector<ExtF> values(count * commits + 1);
     std::vector<Digest> siblings(count * total + 1);
     if (tachyon_mi355x_baby_bear_fri_opening_answer_queries(handle_, indices.data(), count, values.data(),
                                                             siblings.data()) != 1)
       return false;
-    steps->assign(count, {});
-    for (size_t q = 0; q < count; ++q) {
-      size_t at = q * total;
-      for (size_t i = 0; i < commits; ++i) {
-        const size_t n = log_max - i - 1;
-        (*steps)[q].push_back(
-            {values[q * commits + i], std::vector<Digest>(siblings.begin() + at, siblings.begin() + at + n)});
-        at += n;
-      }
-    }
+    steps->clear();
+    for (size_t q = 0; q < count; ++q)
+      steps->push_back(SplitSteps(values.data() + q * commits, siblings.data() + q * total, log_max, commits));
     return true;
   }
 
@@ -297,37 +272,22 @@ class FriOpening {
     if (!handle_ || !challenger || !proof || !opened_values || rounds.empty()) return false;
     const size_t nr = rounds.size();
     std::vector<tachyon_mi355x_baby_bear_fri_round> recs(nr);
-    std::vector<std::vector<const void*>> pts(nr);
-    std::vector<std::vector<size_t>> num(nr);
-    std::vector<std::vector<void*>> outs(nr);
-    std::vector<std::vector<std::vector<ExtF>>> flat(nr);
+    std::vector<PointArgs> args;
+    args.reserve(nr);
     for (size_t r = 0; r < nr; ++r) {
       const Round& round = rounds[r];
       if (!round.tree || round.points.size() != round.tree->leaves().size()) return false;
-      const auto& leaves = round.tree->leaves();
-      const size_t n = leaves.size();
-      pts[r].resize(n), num[r].resize(n), outs[r].resize(n), flat[r].resize(n);
-      for (size_t m = 0; m < n; ++m) {
-        num[r][m] = round.points[m].size();
-        pts[r][m] = round.points[m].data();
-        flat[r][m].resize(num[r][m] * leaves[m].cols);
-        outs[r][m] = flat[r][m].data();
-      }
-      recs[r] = {round.tree->handle(), pts[r].data(), num[r].data(), outs[r].data()};
+      std::vector<size_t> cols;
+      for (const auto& leaf : round.tree->leaves()) cols.push_back(leaf.cols);
+      args.emplace_back(round.points, cols);
+      recs[r] = {round.tree->handle(), args[r].points.data(), args[r].num.data(), args[r].out.data()};
     }
     tachyon_mi355x_baby_bear_fri_proof* p = tachyon_mi355x_baby_bear_fri_opening_prove(
         handle_, challenger.handle(), recs.data(), nr, num_queries, proof_of_work_bits);
     if (!p) return false;
 
-    std::vector<OpenedValuesForRound> opened(nr);
-    for (size_t r = 0; r < nr; ++r) {
-      const auto& leaves = rounds[r].tree->leaves();
-      opened[r].resize(leaves.size());
-      for (size_t m = 0; m < leaves.size(); ++m)
-        for (size_t k = 0; k < num[r][m]; ++k)
-          opened[r][m].emplace_back(flat[r][m].begin() + k * leaves[m].cols,
-                                    flat[r][m].begin() + (k + 1) * leaves[m].cols);
-    }
+    std::vector<OpenedValuesForRound> opened;
+    for (const PointArgs& a : args) opened.push_back(a.Opened());
     FRIProof result;
     const size_t commits = tachyon_mi355x_baby_bear_fri_proof_num_commits(p);
     const uint32_t log_max = input_log_size(0);
@@ -337,23 +297,15 @@ class FriOpening {
                   p, commits ? result.commit_phase_commits.data()->data() : unused.data()) == 1 &&
               tachyon_mi355x_baby_bear_fri_proof_final_eval(p, result.final_eval.data()) == 1 &&
               tachyon_mi355x_baby_bear_fri_proof_pow_witness(p, reinterpret_cast<uint32_t*>(&result.pow_witness)) == 1;
-    size_t total = 0;
-    for (size_t i = 0; i < commits; ++i) total += log_max - i - 1;
     const size_t queries = tachyon_mi355x_baby_bear_fri_proof_num_queries(p);
     result.query_proofs.resize(queries);
     std::vector<ExtF> values(commits + 1);
-    std::vector<Digest> siblings(total + 1);
+    std::vector<Digest> siblings(TotalSiblings(log_max, commits) + 1);
     for (size_t q = 0; ok && q < queries; ++q) {
       QueryProof& qp = result.query_proofs[q];
       result.query_indices.push_back(tachyon_mi355x_baby_bear_fri_proof_query_index(p, q));
       ok = tachyon_mi355x_baby_bear_fri_proof_query_steps(p, q, values.data(), siblings.data()) == 1;
-      size_t at = 0;
-      for (size_t i = 0; ok && i < commits; ++i) {
-        const size_t n = log_max - i - 1;
-        qp.commit_phase_openings.push_back(
-            {values[i], std::vector<Digest>(siblings.begin() + at, siblings.begin() + at + n)});
-        at += n;
-      }
+      if (ok) qp.commit_phase_openings = SplitSteps(values.data(), siblings.data(), log_max, commits);
       for (size_t r = 0; ok && r < nr; ++r) {
         const auto& leaves = rounds[r].tree->leaves();
         BatchOpening opening;
@@ -381,6 +333,50 @@ class FriOpening {
   tachyon_mi355x_baby_bear_fri_opening* handle() { return handle_; }
 
  private:
+  /* digests of all commit-phase openings of one query */
+  static size_t TotalSiblings(uint32_t log_max, size_t commits) {
+    size_t total = 0;
+    for (size_t i = 0; i < commits; ++i) total += log_max - i - 1;
+    return total;
+  }
+
+  /* one query's steps from its sibling values and its digests, tree by tree */
+  static std::vector<CommitPhaseProofStep> SplitSteps(const ExtF* values, const Digest* siblings, uint32_t log_max,
+                                                      size_t commits) {
+    std::vector<CommitPhaseProofStep> steps;
+    for (size_t i = 0; i < commits; ++i) {
+      const size_t n = log_max - i - 1;
+      steps.push_back({values[i], std::vector<Digest>(siblings, siblings + n)});
+      siblings += n;
+    }
+    return steps;
+  }
+
+  /* add_round's points, num_points and opened_values_out for one round's
+   * matrices of `cols` columns, and the opened values the call left in them.
+   * `pts` is referenced, not copied. */
+  struct PointArgs {
+    PointArgs(const std::vector<std::vector<ExtF>>& pts, const std::vector<size_t>& cols) : cols(cols) {
+      for (size_t m = 0; m < cols.size(); ++m) {
+        points.push_back(pts[m].data());
+        num.push_back(pts[m].size());
+        flat.emplace_back(pts[m].size() * cols[m]);
+      }
+      for (auto& f : flat) out.push_back(f.data());
+    }
+    OpenedValuesForRound Opened() const {
+      OpenedValuesForRound result(cols.size());
+      for (size_t m = 0; m < cols.size(); ++m)
+        for (size_t p = 0; p < num[m]; ++p)
+          result[m].emplace_back(flat[m].begin() + p * cols[m], flat[m].begin() + (p + 1) * cols[m]);
+      return result;
+    }
+    std::vector<size_t> cols, num;
+    std::vector<const void*> points;
+    std::vector<void*> out;
+    std::vector<std::vector<ExtF>> flat;
+  };
+
   tachyon_mi355x_baby_bear_fri_opening* handle_ = nullptr;
   uint32_t log_blowup_ = 0;
   std::vector<ExtF> final_poly_;

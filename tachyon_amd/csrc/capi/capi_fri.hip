@@ -3,7 +3,6 @@
 // and phase rules live in fri_validate.h.
 #include "../../../include/tachyon_mi355x.h"
 
-#include <cstring>
 #include <memory>
 
 #include "../common/hip_util.h"
@@ -15,21 +14,13 @@
 using namespace tachyon_amd;
 using fri::Fp4;
 
-// A caller's element is 4 words at any 4-byte alignment (a std::array<F, 4> on
-// the stack); Fp4 is alignas(16), so it is copied, never reinterpreted.
-static Fp4 load_ext(const void* p) {
-  Fp4 v;
-  memcpy(v.c, p, sizeof v.c);
-  return v;
-}
-
 extern "C" {
 
 int tachyon_mi355x_baby_bear4_ops(int op, const void* a, const void* b, void* out, size_t count, void* stream) {
   const bool binary = op == fri::kBb4Add || op == fri::kBb4Sub || op == fri::kBb4Mul;
   if (op < 0 || op >= fri::kBb4NumOps || !a || !out || (binary && !b) || count == 0 || count > (size_t(1) << 28))
     return 0;
-  try {
+  return guarded(0, [&] {
     require_gpu();
     if (!binary) b = a;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -50,21 +41,17 @@ int tachyon_mi355x_baby_bear4_ops(int op, const void* a, const void* b, void* ou
     TA_HIP(hipMemcpyAsync(out, da, bytes, hipMemcpyDeviceToHost, s));
     TA_HIP(hipStreamSynchronize(s));
     return 1;
-  } catch (...) {
-    return 0;
-  }
+  });
 }
 
 tachyon_mi355x_baby_bear_fri_opening* tachyon_mi355x_baby_bear_fri_opening_create(unsigned log_blowup,
                                                                                    int external_matrix, void* stream) {
   if (!fri::log_blowup_ok(log_blowup) || !merkle_tree::external_ok(external_matrix)) return nullptr;
-  try {
+  return guarded<tachyon_mi355x_baby_bear_fri_opening*>(nullptr, [&] {
     auto h = std::make_unique<tachyon_mi355x_baby_bear_fri_opening>();
     h->fri = std::make_unique<fri::FriOpening>(log_blowup, external_matrix, static_cast<hipStream_t>(stream));
     return h.release();
-  } catch (...) {
-    return nullptr;
-  }
+  });
 }
 
 void tachyon_mi355x_baby_bear_fri_opening_destroy(tachyon_mi355x_baby_bear_fri_opening* h) {
@@ -76,11 +63,7 @@ void tachyon_mi355x_baby_bear_fri_opening_destroy(tachyon_mi355x_baby_bear_fri_o
 
 int tachyon_mi355x_baby_bear_fri_opening_begin(tachyon_mi355x_baby_bear_fri_opening* h, const void* alpha) {
   if (!h || !alpha) return 0;
-  try {
-    return h->fri->begin(load_ext(alpha)) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->begin(fri::load_ext(alpha, 0)); });
 }
 
 int tachyon_mi355x_baby_bear_fri_opening_add_round(tachyon_mi355x_baby_bear_fri_opening* h, const void* const* ldes,
@@ -88,11 +71,7 @@ int tachyon_mi355x_baby_bear_fri_opening_add_round(tachyon_mi355x_baby_bear_fri_
                                                    const void* const* points, const size_t* num_points,
                                                    void* const* opened_values_out) {
   if (!h) return 0;
-  try {
-    return h->fri->add_round(ldes, rows, cols, count, points, num_points, opened_values_out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->add_round(ldes, rows, cols, count, points, num_points, opened_values_out); });
 }
 
 size_t tachyon_mi355x_baby_bear_fri_opening_num_inputs(const tachyon_mi355x_baby_bear_fri_opening* h) {
@@ -105,11 +84,7 @@ unsigned tachyon_mi355x_baby_bear_fri_opening_input_log_size(const tachyon_mi355
 
 int tachyon_mi355x_baby_bear_fri_opening_input(tachyon_mi355x_baby_bear_fri_opening* h, size_t k, void* out) {
   if (!h || !out) return 0;
-  try {
-    return h->fri->input(k, out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->input(k, out); });
 }
 
 const void* tachyon_mi355x_baby_bear_fri_opening_input_device_ptr(const tachyon_mi355x_baby_bear_fri_opening* h,
@@ -119,20 +94,12 @@ const void* tachyon_mi355x_baby_bear_fri_opening_input_device_ptr(const tachyon_
 
 int tachyon_mi355x_baby_bear_fri_opening_commit(tachyon_mi355x_baby_bear_fri_opening* h, void* root_out) {
   if (!h || !root_out) return 0;
-  try {
-    return h->fri->commit(root_out) == 1 ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->commit(root_out) == 1; });
 }
 
 int tachyon_mi355x_baby_bear_fri_opening_fold(tachyon_mi355x_baby_bear_fri_opening* h, const void* beta) {
   if (!h || !beta) return 0;
-  try {
-    return h->fri->fold(load_ext(beta)) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->fold(fri::load_ext(beta, 0)); });
 }
 
 size_t tachyon_mi355x_baby_bear_fri_opening_num_commits(const tachyon_mi355x_baby_bear_fri_opening* h) {
@@ -141,21 +108,13 @@ size_t tachyon_mi355x_baby_bear_fri_opening_num_commits(const tachyon_mi355x_bab
 
 int tachyon_mi355x_baby_bear_fri_opening_final_poly(tachyon_mi355x_baby_bear_fri_opening* h, void* out) {
   if (!h || !out) return 0;
-  try {
-    return h->fri->final_poly(out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->final_poly(out); });
 }
 
 int tachyon_mi355x_baby_bear_fri_opening_answer_query(tachyon_mi355x_baby_bear_fri_opening* h, size_t index,
                                                       void* sibling_values_out, void* siblings_out) {
   if (!h) return 0;
-  try {
-    return h->fri->answer_query(index, sibling_values_out, siblings_out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->answer_query(index, sibling_values_out, siblings_out); });
 }
 
 unsigned tachyon_mi355x_baby_bear_fri_opening_last_launches(const tachyon_mi355x_baby_bear_fri_opening* h) {

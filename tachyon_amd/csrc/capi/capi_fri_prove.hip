@@ -23,20 +23,13 @@ extern "C" {
 
 Challenger* tachyon_mi355x_baby_bear_duplex_challenger_create(int external_matrix, unsigned rate) {
   if (!merkle_tree::external_ok(external_matrix) || !fri::challenger_rate_ok(rate)) return nullptr;
-  try {
-    return new Challenger{fri::DuplexChallenger(external_matrix, rate), nullptr};
-  } catch (...) {
-    return nullptr;
-  }
+  return guarded<Challenger*>(
+      nullptr, [&] { return new Challenger{fri::DuplexChallenger(external_matrix, rate), nullptr}; });
 }
 
 Challenger* tachyon_mi355x_baby_bear_duplex_challenger_clone(const Challenger* c) {
   if (!c) return nullptr;
-  try {
-    return new Challenger{c->challenger, nullptr};
-  } catch (...) {
-    return nullptr;
-  }
+  return guarded<Challenger*>(nullptr, [&] { return new Challenger{c->challenger, nullptr}; });
 }
 
 void tachyon_mi355x_baby_bear_duplex_challenger_destroy(Challenger* c) {
@@ -85,13 +78,11 @@ int tachyon_mi355x_baby_bear_duplex_challenger_state(const Challenger* c, uint32
 int tachyon_mi355x_baby_bear_duplex_challenger_grind_range(Challenger* c, unsigned bits, uint64_t from, uint64_t to,
                                                            uint32_t* witness_out, void* stream) {
   if (!c || !witness_out || !fri::grind_args_ok(bits, from, to)) return 0;
-  try {
+  return guarded(0, [&] {
     require_gpu();
     if (!c->grind) c->grind = std::make_unique<DeviceBuffer>();
-    return fri::grind(c->challenger, bits, from, to, witness_out, *c->grind, static_cast<hipStream_t>(stream)) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+    return fri::grind(c->challenger, bits, from, to, witness_out, *c->grind, static_cast<hipStream_t>(stream));
+  });
 }
 
 int tachyon_mi355x_baby_bear_duplex_challenger_grind(Challenger* c, unsigned bits, uint32_t* witness_out,
@@ -102,21 +93,13 @@ int tachyon_mi355x_baby_bear_duplex_challenger_grind(Challenger* c, unsigned bit
 int tachyon_mi355x_baby_bear_merkle_tree_open_batch(tachyon_mi355x_baby_bear_merkle_tree* tree, const size_t* indices,
                                                     size_t count, void* const* rows_out, void* siblings_out) {
   if (!tree || !indices || !rows_out) return 0;
-  try {
-    return tree->tree->open_batch(indices, count, rows_out, siblings_out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return tree->tree->open_batch(indices, count, rows_out, siblings_out); });
 }
 
 int tachyon_mi355x_baby_bear_fri_opening_answer_queries(tachyon_mi355x_baby_bear_fri_opening* h, const size_t* indices,
                                                         size_t count, void* sibling_values_out, void* siblings_out) {
   if (!h || !indices) return 0;
-  try {
-    return h->fri->answer_queries(indices, count, sibling_values_out, siblings_out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return h->fri->answer_queries(indices, count, sibling_values_out, siblings_out); });
 }
 
 FriProof* tachyon_mi355x_baby_bear_fri_opening_prove(tachyon_mi355x_baby_bear_fri_opening* h, Challenger* challenger,
@@ -124,7 +107,7 @@ FriProof* tachyon_mi355x_baby_bear_fri_opening_prove(tachyon_mi355x_baby_bear_fr
                                                      size_t num_rounds, size_t num_queries,
                                                      unsigned proof_of_work_bits) {
   if (!h || !challenger || !rounds || num_rounds == 0) return nullptr;
-  try {
+  return guarded<FriProof*>(nullptr, [&]() -> FriProof* {
     std::vector<fri::ProveRound> rs(num_rounds);
     for (size_t r = 0; r < num_rounds; ++r) {
       if (!rounds[r].tree) return nullptr;
@@ -135,9 +118,7 @@ FriProof* tachyon_mi355x_baby_bear_fri_opening_prove(tachyon_mi355x_baby_bear_fr
     if (!h->fri->prove(challenger->challenger, rs.data(), num_rounds, num_queries, proof_of_work_bits, &proof->proof))
       return nullptr;
     return proof.release();
-  } catch (...) {
-    return nullptr;
-  }
+  });
 }
 
 void tachyon_mi355x_baby_bear_fri_proof_destroy(FriProof* proof) {

@@ -18,7 +18,7 @@ extern "C" {
 
 int tachyon_mi355x_poseidon2_baby_bear_permute(int external_matrix, void* states, size_t count, void* stream) {
   if (!merkle_tree::external_ok(external_matrix) || !states || count == 0 || count > (size_t(1) << 32)) return 0;
-  try {
+  return guarded(0, [&] {
     require_gpu();
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (is_device_pointer(states)) {
@@ -34,20 +34,16 @@ int tachyon_mi355x_poseidon2_baby_bear_permute(int external_matrix, void* states
     TA_HIP(hipMemcpyAsync(states, d.as<void>(), bytes, hipMemcpyDeviceToHost, s));
     TA_HIP(hipStreamSynchronize(s));
     return 1;
-  } catch (...) {
-    return 0;
-  }
+  });
 }
 
 tachyon_mi355x_baby_bear_merkle_tree* tachyon_mi355x_baby_bear_merkle_tree_create(int external_matrix, void* stream) {
   if (!merkle_tree::external_ok(external_matrix)) return nullptr;
-  try {
+  return guarded<tachyon_mi355x_baby_bear_merkle_tree*>(nullptr, [&] {
     auto h = std::make_unique<tachyon_mi355x_baby_bear_merkle_tree>();
     h->tree = std::make_unique<hash::BbMerkleTree>(external_matrix, static_cast<hipStream_t>(stream));
     return h.release();
-  } catch (...) {
-    return nullptr;
-  }
+  });
 }
 
 void tachyon_mi355x_baby_bear_merkle_tree_destroy(tachyon_mi355x_baby_bear_merkle_tree* tree) {
@@ -61,20 +57,12 @@ int tachyon_mi355x_baby_bear_merkle_tree_build(tachyon_mi355x_baby_bear_merkle_t
                                                const void* const* matrices, const size_t* rows, const size_t* cols,
                                                size_t count, unsigned flags) {
   if (!tree || !matrices || !rows || !cols || count == 0) return 0;
-  try {
-    return tree->tree->build(matrices, rows, cols, count, flags) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return tree->tree->build(matrices, rows, cols, count, flags); });
 }
 
 int tachyon_mi355x_baby_bear_merkle_tree_root(tachyon_mi355x_baby_bear_merkle_tree* tree, void* out) {
   if (!tree || !out) return 0;
-  try {
-    return tree->tree->root(out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return tree->tree->root(out); });
 }
 
 size_t tachyon_mi355x_baby_bear_merkle_tree_num_layers(const tachyon_mi355x_baby_bear_merkle_tree* tree) {
@@ -87,11 +75,7 @@ size_t tachyon_mi355x_baby_bear_merkle_tree_layer_size(const tachyon_mi355x_baby
 
 int tachyon_mi355x_baby_bear_merkle_tree_layer(tachyon_mi355x_baby_bear_merkle_tree* tree, size_t k, void* out) {
   if (!tree || !out) return 0;
-  try {
-    return tree->tree->layer(k, out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return tree->tree->layer(k, out); });
 }
 
 const void* tachyon_mi355x_baby_bear_merkle_tree_layers_device_ptr(const tachyon_mi355x_baby_bear_merkle_tree* tree) {
@@ -101,11 +85,7 @@ const void* tachyon_mi355x_baby_bear_merkle_tree_layers_device_ptr(const tachyon
 int tachyon_mi355x_baby_bear_merkle_tree_open(tachyon_mi355x_baby_bear_merkle_tree* tree, size_t index,
                                               void* const* rows_out, void* siblings_out) {
   if (!tree || !rows_out) return 0;
-  try {
-    return tree->tree->open(index, rows_out, siblings_out) ? 1 : 0;
-  } catch (...) {
-    return 0;
-  }
+  return guarded(0, [&] { return tree->tree->open(index, rows_out, siblings_out); });
 }
 
 unsigned tachyon_mi355x_baby_bear_merkle_tree_last_launches(const tachyon_mi355x_baby_bear_merkle_tree* tree) {
@@ -118,12 +98,10 @@ void* tachyon_mi355x_baby_bear_merkle_tree_stream(tachyon_mi355x_baby_bear_merkl
 
 double tachyon_mi355x_baby_bear_mul_rate(size_t threads, unsigned iters) {
   if (threads == 0 || iters == 0 || threads > (size_t(1) << 28)) return 0;
-  try {
+  return guarded(0.0, [&] {
     require_gpu();
     return hash::bb31_mul_rate(threads, iters, nullptr);
-  } catch (...) {
-    return 0;
-  }
+  });
 }
 
 }  // extern "C"

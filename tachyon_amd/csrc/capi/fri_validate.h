@@ -6,27 +6,19 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../common/bits.h"
+
 namespace tachyon_amd::fri {
 
 inline constexpr unsigned kMaxLogRows = 27;               // BabyBear's two-adicity
 inline constexpr unsigned kMaxLogBlowup = 26;             // a fold step needs a root of order 2 rows
 inline constexpr size_t kMaxCols = size_t(1) << 24;       // the tree's limit on one row
 
-inline bool is_pow2(size_t n) { return n != 0 && (n & (n - 1)) == 0; }
+using bits::bit_reverse;
+using bits::is_pow2;
 
 // log2 of a power of two
-inline unsigned log2_exact(size_t n) {
-  unsigned l = 0;
-  while ((size_t(1) << l) < n) ++l;
-  return l;
-}
-
-// x reversed over `bits` bits
-inline size_t bit_reverse(size_t x, unsigned bits) {
-  size_t r = 0;
-  for (unsigned b = 0; b < bits; ++b) r |= ((x >> b) & 1) << (bits - 1 - b);
-  return r;
-}
+inline unsigned log2_exact(size_t n) { return bits::ceil_log2(n); }
 
 inline bool log_blowup_ok(unsigned log_blowup) { return log_blowup >= 1 && log_blowup <= kMaxLogBlowup; }
 

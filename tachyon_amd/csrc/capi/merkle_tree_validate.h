@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../common/bits.h"
+
 namespace tachyon_amd::merkle_tree {
 
 inline constexpr unsigned kFlagBitReversed = 1u;  // TACHYON_MI355X_MERKLE_BIT_REVERSED
@@ -18,27 +20,10 @@ inline constexpr size_t kMaxRowWords = size_t(1) << 24; // words of one concaten
 // external_matrix ids: 0 Horizen, 1 Plonky3
 inline bool external_ok(int id) { return id == 0 || id == 1; }
 
-inline size_t bit_ceil(size_t n) {
-  size_t p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
-// ceil(log2(n)) for n >= 1
-inline unsigned ceil_log2(size_t n) {
-  unsigned l = 0;
-  while ((size_t(1) << l) < n) ++l;
-  return l;
-}
-
-inline bool is_pow2(size_t n) { return n != 0 && (n & (n - 1)) == 0; }
-
-// x reversed over `bits` bits
-inline size_t bit_reverse(size_t x, unsigned bits) {
-  size_t r = 0;
-  for (unsigned b = 0; b < bits; ++b) r |= ((x >> b) & 1) << (bits - 1 - b);
-  return r;
-}
+using bits::bit_ceil;
+using bits::bit_reverse;
+using bits::ceil_log2;
+using bits::is_pow2;
 
 // One digest layer: the matrices order[first .. first + count) are hashed into
 // it (count == 0: plain compression), `rows` their common height.

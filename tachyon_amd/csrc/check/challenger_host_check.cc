@@ -1,4 +1,4 @@
-// The host Poseidon2 and DuplexChallenger headers on their own, with a plain
+// The Poseidon2 and DuplexChallenger headers on the host, on their own, with a plain
 // host compiler and no library: the known answers of tests/test_challenger.py
 // walked in C++, so that the headers can be run under the host sanitizers
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -32,7 +32,7 @@ bool equal_canonical(const uint32_t* mont, const uint32_t* want, size_t n) {
 }  // namespace
 
 int main() {
-  namespace host = poseidon2_bb_host;
+  namespace host = poseidon2_bb;
 
   // Poseidon2 of 0..15 (Horizen) and of 16 times p - 1: tests/golden/poseidon2_baby_bear.json
   const uint32_t horizen_0_to_15[16] = {1699737005, 296394369,  268410240, 828329642, 1491697358, 1128780676,

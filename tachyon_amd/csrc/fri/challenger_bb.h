@@ -10,7 +10,7 @@
 #include <cstdint>
 
 #include "../field/bb31.h"
-#include "../hash/poseidon2_bb_host.h"
+#include "../hash/poseidon2_bb.h"
 
 namespace tachyon_amd::fri {
 
@@ -87,7 +87,7 @@ class DuplexChallenger {
   void duplex() {
     for (unsigned i = 0; i < num_in_; ++i) state_[i] = in_[i];
     num_in_ = 0;
-    poseidon2_bb_host::permute(external_, state_);
+    poseidon2_bb::permute(external_, state_);
     for (unsigned i = 0; i < kChallengerWidth; ++i) out_[i] = state_[i];
     num_out_ = kChallengerWidth;
   }

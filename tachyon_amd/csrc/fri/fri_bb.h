@@ -123,11 +123,13 @@ class FriOpening {
   bool fold(const Fp4& beta);
   size_t num_commits() const { return num_commits_; }
   bool final_poly(void* out);  // waits
-  bool answer_query(size_t index, void* sibling_values_out, void* siblings_out);  // waits once
-  // answer_query at `count` indices (fri_prove_bb.hip), query q's part in
-  // answer_query's layout at q times its size.  One launch, two copies, one
-  // wait.  False, with nothing written, for a null pointer, count 0 or above
-  // kMaxQueries, or an index answer_query refuses.
+  // answer_queries at one index, except that with no commit-phase tree the
+  // outputs are not looked at.  Waits once.
+  bool answer_query(size_t index, void* sibling_values_out, void* siblings_out);
+  // The queries at `count` indices (fri_prove_bb.hip): per query, first array
+  // 4 words per commit-phase tree, second 8 words per sibling digest, tree by
+  // tree.  One launch, two copies, one wait.  False, with nothing written, for a
+  // null pointer, count 0 or above kMaxQueries, or an index out of range.
   static constexpr size_t kMaxQueries = size_t(1) << 16;
   bool answer_queries(const size_t* indices, size_t count, void* sibling_values_out, void* siblings_out);
 
@@ -179,7 +181,6 @@ class FriOpening {
   std::vector<std::unique_ptr<DeviceBuffer>> folds_;        // folds_[i]: the vector after fold step i + 1
   std::vector<std::unique_ptr<hash::BbMerkleTree>> trees_;  // trees_[i] over folded(i)
   size_t num_commits_ = 0;
-  DeviceBuffer query_;  // a query's gathered answer
   DeviceBuffer queries_;  // answer_queries: the indices, then the gathered answers
   DeviceBuffer grind_;    // prove: the grind's device word
 };

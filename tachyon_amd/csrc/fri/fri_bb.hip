@@ -15,8 +15,6 @@
 //                       LDS as merkle_bb.hip's hash_kernel does, then
 //                       ro[i] += sum_p alpha^offset_p (rr[i] - rys_p) inv_p[i]
 //   fold_kernel         FoldMatrix plus the equal-size input
-//   query_kernel        one query's sibling values and digests of every
-//                       commit-phase tree, gathered for one copy
 #include "fri_bb.h"
 
 #include <cstring>
@@ -34,7 +32,6 @@ constexpr unsigned kInterpBlocks = 2048;  // at most about this many interpolati
 constexpr unsigned kTileRows = kBlock;  // positions of a reduce block, one lane each
 constexpr unsigned kTileCols = 32;     // columns staged at a time
 constexpr unsigned kPitch = kTileCols + 1;
-constexpr unsigned kMaxCommits = kMaxLogRows;
 
 // base^(2^j), Montgomery: the power of any exponent is a product over its set bits
 struct PowTable {
@@ -271,31 +268,6 @@ __global__ __launch_bounds__(kBlock) void fold_kernel(const Fp4* v, const Fp4* a
   Fp4 s = f4::add(f4::mul(lo_f, load4(v + 2 * (size_t)r)), f4::mul(hi_f, load4(v + 2 * (size_t)r + 1)));
   if (add_in) s = f4::add(s, load4(add_in + r));
   store4(out + r, s);
-}
-
-struct QueryArgs {
-  const Fp4* folded[kMaxCommits];
-  const uint32_t* layers[kMaxCommits];
-  uint32_t sib_off[kMaxCommits];  // digests of the trees before this one
-  uint32_t log_max;
-  uint32_t index;
-  uint32_t* vals;  // 4 words per tree
-  uint32_t* sibs;  // 8 words per digest
-};
-
-// block i: tree i over the folded vector of 2^(log_max - i) elements
-__global__ __launch_bounds__(kBlock) void query_kernel(const QueryArgs a) {
-  const uint32_t i = blockIdx.x, t = threadIdx.x;
-  const uint32_t index_i = a.index >> i, pair = index_i >> 1;
-  const uint32_t nsib = a.log_max - i - 1;  // the tree has 2^nsib leaves
-  if (t < 4) a.vals[4 * i + t] = reinterpret_cast<const uint32_t*>(a.folded[i] + (index_i ^ 1))[t];
-  if (t < 8 * nsib) {
-    const uint32_t k = t / 8, j = t % 8;
-    const size_t leaves = size_t(1) << nsib;
-    const size_t offset = 2 * leaves - ((2 * leaves) >> k);  // digests before layer k
-    const size_t sibling = (pair >> k) ^ 1;
-    a.sibs[8 * (size_t)(a.sib_off[i] + k) + j] = a.layers[i][8 * (offset + sibling) + j];
-  }
 }
 
 // ---------------------------------------------------------------- host side
@@ -600,35 +572,6 @@ bool FriOpening::fold(const Fp4& beta) {
 bool FriOpening::final_poly(void* out) {
   if (!ended(phase_) || !out) return false;
   TA_HIP(hipMemcpyAsync(out, folded(num_commits_), sizeof(Fp4) << phase_.log_size, hipMemcpyDeviceToHost, stream_));
-  TA_HIP(hipStreamSynchronize(stream_));
-  return true;
-}
-
-bool FriOpening::answer_query(size_t index, void* sibling_values_out, void* siblings_out) {
-  if (!can_answer(phase_, index)) return false;
-  if (num_commits_ == 0) return true;  // nothing was committed: nothing to open
-  if (!sibling_values_out) return false;
-  const size_t total = query_total_siblings(phase_.log_max, (unsigned)num_commits_);
-  if (total && !siblings_out) return false;
-  const size_t val_bytes = num_commits_ * sizeof(Fp4), sib_bytes = total * 8 * sizeof(uint32_t);
-  uint8_t* d = static_cast<uint8_t*>(query_.ensure(val_bytes + std::max<size_t>(sib_bytes, 32)));
-  QueryArgs a{};
-  uint32_t off = 0;
-  for (size_t i = 0; i < num_commits_; ++i) {
-    a.folded[i] = folded(i);
-    a.layers[i] = trees_[i]->layers_device();
-    a.sib_off[i] = off;
-    off += query_num_siblings(phase_.log_max, (unsigned)i);
-  }
-  a.log_max = phase_.log_max;
-  a.index = (uint32_t)index;
-  a.vals = reinterpret_cast<uint32_t*>(d);
-  a.sibs = reinterpret_cast<uint32_t*>(d + val_bytes);
-  hipLaunchKernelGGL(query_kernel, dim3((unsigned)num_commits_), dim3(kBlock), 0, stream_, a);
-  TA_HIP(hipGetLastError());
-  launches_ = 1;
-  TA_HIP(hipMemcpyAsync(sibling_values_out, d, val_bytes, hipMemcpyDeviceToHost, stream_));
-  if (total) TA_HIP(hipMemcpyAsync(siblings_out, d + val_bytes, sib_bytes, hipMemcpyDeviceToHost, stream_));
   TA_HIP(hipStreamSynchronize(stream_));
   return true;
 }

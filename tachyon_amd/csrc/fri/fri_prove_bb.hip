@@ -1,8 +1,8 @@
 // The queries of a FRI opening at many indices at once, and the whole opening
 // proof in one call (see fri_bb.h):
-//   queries_kernel   fri_bb.hip's query_kernel over a query dimension: block
-//                    (q, i) gathers query q's sibling value and digests of
-//                    commit-phase tree i
+//   queries_kernel   block (q, i) gathers query q's sibling value and digests
+//                    of commit-phase tree i, over the folded vector of
+//                    2^(log_max - i) elements; a single query is a batch of one
 //   prove            TwoAdicFRI::CreateOpeningProof followed by fri::Prove
 //                    (two_adic_fri.h:96-219, prove.h:121-159) in the
 //                    reference's transcript order, with the grind on the GPU
@@ -40,13 +40,7 @@ __global__ __launch_bounds__(kBlock) void queries_kernel(const QueriesArgs a) {
   const uint32_t nsib = a.log_max - i - 1;  // the tree has 2^nsib leaves
   if (t < 4)
     a.vals[4 * ((size_t)q * a.num_commits + i) + t] = reinterpret_cast<const uint32_t*>(a.folded[i] + (index_i ^ 1))[t];
-  if (t < 8 * nsib) {
-    const uint32_t k = t / 8, j = t % 8;
-    const size_t leaves = size_t(1) << nsib;
-    const size_t offset = 2 * leaves - ((2 * leaves) >> k);  // digests before layer k
-    const size_t sibling = (pair >> k) ^ 1;
-    a.sibs[8 * ((size_t)q * a.total_sibs + a.sib_off[i] + k) + j] = a.layers[i][8 * (offset + sibling) + j];
-  }
+  hash::gather_siblings(a.layers[i], nsib, pair, a.sibs + 8 * ((size_t)q * a.total_sibs + a.sib_off[i]), t);
 }
 
 }  // namespace
@@ -85,6 +79,12 @@ bool FriOpening::answer_queries(const size_t* indices, size_t count, void* sibli
   if (total) TA_HIP(hipMemcpyAsync(siblings_out, a.sibs, sib_bytes, hipMemcpyDeviceToHost, stream_));
   TA_HIP(hipStreamSynchronize(stream_));
   return true;
+}
+
+bool FriOpening::answer_query(size_t index, void* sibling_values_out, void* siblings_out) {
+  // nothing was committed: nothing to open, whatever the outputs are
+  if (num_commits_ == 0) return can_answer(phase_, index);
+  return answer_queries(&index, 1, sibling_values_out, siblings_out);
 }
 
 bool FriOpening::prove(DuplexChallenger& challenger, const ProveRound* rounds, size_t num_rounds, size_t num_queries,

@@ -28,6 +28,22 @@ void poseidon2_bb_permute(int external, uint32_t* d_states, size_t count, hipStr
 // products in each of `threads` lanes: the VALU yardstick of the probe
 double bb31_mul_rate(size_t threads, unsigned iters, hipStream_t stream);
 
+// The sibling digests on the path from leaf `index` of a tree of 2^log_leaves
+// leaves whose layers lie in `layers` as BbMerkleTree keeps them (layer k
+// begins 2 leaves - (2 leaves >> k) digests in): the sibling in layer k goes to
+// dst + 8 k, 8 lanes a digest, so lane t writes word t.  Every lane of a block
+// of at least 8 log_leaves lanes calls it with its own `lane`.
+__device__ __forceinline__ void gather_siblings(const uint32_t* layers, uint32_t log_leaves, uint32_t index,
+                                                uint32_t* dst, uint32_t lane) {
+  if (lane < 8 * log_leaves) {
+    const uint32_t k = lane / 8, j = lane % 8;
+    const size_t leaves = size_t(1) << log_leaves;
+    const size_t offset = 2 * leaves - ((2 * leaves) >> k);  // digests before layer k
+    const size_t sibling = (index >> k) ^ 1;
+    dst[lane] = layers[8 * (offset + sibling) + j];
+  }
+}
+
 class BbMerkleTree {
  public:
   static constexpr size_t kDigestWords = 8;
@@ -56,7 +72,7 @@ class BbMerkleTree {
   bool root(void* out);
   // rows_out[m]: cols[m] words of matrix m (the caller's order), zeros for a row
   // past its height; siblings_out: (num_layers - 1) digests.  False for
-  // index >= layer_size(0).
+  // index >= layer_size(0).  It is open_batch at one index.
   bool open(size_t index, void* const* rows_out, void* siblings_out);
   // open() at `count` indices (merkle_open_bb.hip): rows_out[m] receives count
   // rows of cols[m] words, siblings_out count * (num_layers - 1) digests, query

@@ -14,7 +14,6 @@
 //                    workgroup, instead of one launch of a few lanes per layer
 #include "merkle_bb.h"
 
-#include <cstring>
 #include <memory>
 #include <type_traits>
 
@@ -371,29 +370,5 @@ bool BbMerkleTree::layer(size_t k, void* out) {
 }
 
 bool BbMerkleTree::root(void* out) { return built() && layer(plan_.levels.size() - 1, out); }
-
-bool BbMerkleTree::open(size_t index, void* const* rows_out, void* siblings_out) {
-  if (!built() || !rows_out || index >= plan_.levels[0].size) return false;
-  if (plan_.log_max > 0 && !siblings_out) return false;
-  for (size_t m = 0; m < mats_.size(); ++m)
-    if (!rows_out[m]) return false;
-  for (size_t m = 0; m < mats_.size(); ++m) {
-    size_t r;
-    const size_t bytes = cols_[m] * sizeof(uint32_t);
-    if (merkle_tree::open_row(index, plan_.log_max, rows_[m], flags_, &r))
-      TA_HIP(hipMemcpyAsync(rows_out[m], mats_[m] + r * cols_[m], bytes, hipMemcpyDeviceToHost, stream_));
-    else
-      memset(rows_out[m], 0, bytes);
-  }
-  const uint32_t* layer = layers_.as<uint32_t>();
-  for (unsigned k = 0; k < plan_.log_max; ++k) {
-    const size_t sibling = (index >> k) ^ 1;
-    TA_HIP(hipMemcpyAsync(static_cast<uint32_t*>(siblings_out) + k * kDigestWords, layer + sibling * kDigestWords,
-                          kDigestWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-    layer += plan_.levels[k].size * kDigestWords;
-  }
-  TA_HIP(hipStreamSynchronize(stream_));
-  return true;
-}
 
 }  // namespace tachyon_amd::hash

@@ -1,4 +1,4 @@
-// FieldMerkleTreeMMCS's openings at many indices at once (see merkle_bb.h):
+// FieldMerkleTreeMMCS's openings, at one index or many at once (see merkle_bb.h):
 //   open_batch_kernel   block (q, job): job m < matrices copies the opened row
 //                       of matrix m for query q, the lanes along its columns (a
 //                       row is one contiguous run on both sides); the last job
@@ -52,16 +52,14 @@ __global__ __launch_bounds__(kBlock) void open_batch_kernel(const OpenArgs a) {
     for (uint32_t c = t; c < m.cols; c += kBlock) dst[c] = present ? src[c] : 0u;
     return;
   }
-  if (t < 8 * a.log_max) {
-    const uint32_t k = t / 8, j = t % 8;
-    const size_t leaves = size_t(1) << a.log_max;
-    const size_t offset = 2 * leaves - ((2 * leaves) >> k);  // digests before layer k
-    const size_t sibling = (index >> k) ^ 1;
-    a.out[a.sib_at + 8 * ((size_t)q * a.log_max + k) + j] = a.layers[8 * (offset + sibling) + j];
-  }
+  gather_siblings(a.layers, a.log_max, index, a.out + a.sib_at + 8 * (size_t)q * a.log_max, t);
 }
 
 }  // namespace
+
+bool BbMerkleTree::open(size_t index, void* const* rows_out, void* siblings_out) {
+  return open_batch(&index, 1, rows_out, siblings_out);
+}
 
 bool BbMerkleTree::open_batch(const size_t* indices, size_t count, void* const* rows_out, void* siblings_out) {
   if (!built() || !indices || !rows_out || count == 0 || count > kMaxBatch) return false;

@@ -40,6 +40,26 @@ def _ext(value: bytes):
     return ctypes.create_string_buffer(value, EXT_BYTES)
 
 
+def _point_args(points, cols):
+    """add_round's points, num_points and opened_values_out for matrices of
+    `cols` columns, then the output buffers and the point buffers (which the
+    pointers need alive)."""
+    n = len(cols)
+    pbufs = [ctypes.create_string_buffer(b"".join(bytes(_ext(z).raw) for z in ps), max(1, len(ps) * EXT_BYTES))
+             for ps in points]
+    obufs = [ctypes.create_string_buffer(max(1, len(ps) * c * EXT_BYTES)) for ps, c in zip(points, cols)]
+    pptrs = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in pbufs])
+    nps = (ctypes.c_size_t * max(1, n))(*[len(ps) for ps in points])
+    optrs = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in obufs])
+    return pptrs, nps, optrs, obufs, pbufs
+
+
+def _opened_values(points, cols, obufs):
+    """per matrix, per point, the opened values' bytes (cols elements)"""
+    return [[b.raw[p * c * EXT_BYTES:(p + 1) * c * EXT_BYTES] for p in range(len(ps))]
+            for ps, c, b in zip(points, cols, obufs)]
+
+
 class FriOpening:
     """The prover side of TwoAdicFRI::CreateOpeningProof: reduce_openings() per
     commit round, commit_phase(on_commit), answer_query(index), final_eval."""
@@ -76,20 +96,10 @@ class FriOpening:
         ptrs = (ctypes.c_void_p * max(1, n))(*[m[0] for m in mats])
         rows = (ctypes.c_size_t * max(1, n))(*[m[1] for m in mats])
         cols = (ctypes.c_size_t * max(1, n))(*[m[2] for m in mats])
-        pbufs = [ctypes.create_string_buffer(b"".join(bytes(_ext(z).raw) for z in ps), max(1, len(ps) * EXT_BYTES))
-                 for ps in points]
-        obufs = [ctypes.create_string_buffer(max(1, len(ps) * int(m[2]) * EXT_BYTES)) for ps, m in zip(points, mats)]
-        pptrs = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in pbufs])
-        nps = (ctypes.c_size_t * max(1, n))(*[len(ps) for ps in points])
-        optrs = (ctypes.c_void_p * max(1, n))(*[ctypes.addressof(b) for b in obufs])
+        widths = [int(m[2]) for m in mats]
+        pptrs, nps, optrs, obufs, _keep = _point_args(points, widths)
         ok = lib().tachyon_mi355x_baby_bear_fri_opening_add_round(self._h, ptrs, rows, cols, n, pptrs, nps, optrs) == 1
-        if not ok:
-            return None
-        out = []
-        for ps, m, b in zip(points, mats, obufs):
-            w = int(m[2]) * EXT_BYTES
-            out.append([b.raw[p * w:(p + 1) * w] for p in range(len(ps))])
-        return out
+        return _opened_values(points, widths, obufs) if ok else None
 
     def add_round(self, mats, points):
         """mats: (bytes, rows, cols) per row-major host matrix."""
@@ -183,12 +193,7 @@ class FriOpening:
         sibs = ctypes.create_string_buffer(max(1, sum(counts) * DIGEST_BYTES))
         if lib().tachyon_mi355x_baby_bear_fri_opening_answer_query(self._h, index, vals, sibs) != 1:
             return None
-        out, at = [], 0
-        for i, c in enumerate(counts):
-            out.append((vals.raw[i * EXT_BYTES:(i + 1) * EXT_BYTES],
-                        [sibs.raw[(at + k) * DIGEST_BYTES:(at + k + 1) * DIGEST_BYTES] for k in range(c)]))
-            at += c
-        return out
+        return _split_steps(vals.raw, sibs.raw, counts)
 
     def answer_queries(self, indices):
         """answer_query() at every index with one launch: a list of
@@ -219,16 +224,9 @@ class FriOpening:
         recs = (FriRound * max(1, n))()
         keep, outs = [], []
         for r, (tree, points) in enumerate(rounds):
-            cols = tree._cols
-            if len(points) != len(cols):
+            if len(points) != len(tree._cols):
                 raise ValueError("one list of points per matrix of the round's tree")
-            m = len(cols)
-            pbufs = [ctypes.create_string_buffer(b"".join(bytes(_ext(z).raw) for z in ps), max(1, len(ps) * EXT_BYTES))
-                     for ps in points]
-            obufs = [ctypes.create_string_buffer(max(1, len(ps) * c * EXT_BYTES)) for ps, c in zip(points, cols)]
-            pptrs = (ctypes.c_void_p * max(1, m))(*[ctypes.addressof(b) for b in pbufs])
-            nps = (ctypes.c_size_t * max(1, m))(*[len(ps) for ps in points])
-            optrs = (ctypes.c_void_p * max(1, m))(*[ctypes.addressof(b) for b in obufs])
+            pptrs, nps, optrs, obufs, pbufs = _point_args(points, tree._cols)
             recs[r] = FriRound(tree._h, pptrs, nps, optrs)
             keep.append((pbufs, pptrs, nps, optrs))
             outs.append(obufs)
@@ -236,13 +234,7 @@ class FriOpening:
                                                              proof_of_work_bits)
         if not h:
             return None
-        opened = []
-        for (tree, points), obufs in zip(rounds, outs):
-            per_round = []
-            for ps, c, b in zip(points, tree._cols, obufs):
-                w = c * EXT_BYTES
-                per_round.append([b.raw[p * w:(p + 1) * w] for p in range(len(ps))])
-            opened.append(per_round)
+        opened = [_opened_values(points, tree._cols, obufs) for (tree, points), obufs in zip(rounds, outs)]
         proof = FriProof(h, self.input_log_size(0), [list(tree._cols) for tree, _ in rounds],
                          [tree.num_layers - 1 for tree, _ in rounds])
         return proof, opened

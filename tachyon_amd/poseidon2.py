@@ -127,13 +127,10 @@ class FieldMerkleTree:
         n = self.num_layers
         if n == 0 or index < 0:
             return None
-        rows = [ctypes.create_string_buffer(max(1, c * WORD)) for c in self._cols]
-        ptrs = (ctypes.c_void_p * max(1, len(rows)))(*[ctypes.addressof(r) for r in rows])
-        sib = ctypes.create_string_buffer(max(1, (n - 1) * DIGEST_BYTES))
+        rows, ptrs, sib = self._opening_buffers(1, n - 1)
         if lib().tachyon_mi355x_baby_bear_merkle_tree_open(self._h, index, ptrs, sib) != 1:
             return None
-        return ([r.raw[:c * WORD] for r, c in zip(rows, self._cols)],
-                [sib.raw[k * DIGEST_BYTES:(k + 1) * DIGEST_BYTES] for k in range(n - 1)])
+        return self._openings(rows, sib, 1, n - 1)[0]
 
     def open_batch(self, indices):
         """open() at every index with one gather launch: a list of open()'s
@@ -141,17 +138,25 @@ class FieldMerkleTree:
         n, count = self.num_layers, len(indices)
         if n == 0 or any(i < 0 for i in indices):
             return None
-        rows = [ctypes.create_string_buffer(max(1, count * c * WORD)) for c in self._cols]
-        ptrs = (ctypes.c_void_p * max(1, len(rows)))(*[ctypes.addressof(r) for r in rows])
-        sib = ctypes.create_string_buffer(max(1, count * (n - 1) * DIGEST_BYTES))
+        rows, ptrs, sib = self._opening_buffers(count, n - 1)
         idx = (ctypes.c_size_t * max(1, count))(*indices)
         if lib().tachyon_mi355x_baby_bear_merkle_tree_open_batch(self._h, idx, count, ptrs, sib) != 1:
             return None
+        return self._openings(rows, sib, count, n - 1)
+
+    def _opening_buffers(self, count, nsib):
+        """rows_out's buffers, rows_out and siblings_out for `count` indices of `nsib` siblings each"""
+        rows = [ctypes.create_string_buffer(max(1, count * c * WORD)) for c in self._cols]
+        ptrs = (ctypes.c_void_p * max(1, len(rows)))(*[ctypes.addressof(r) for r in rows])
+        return rows, ptrs, ctypes.create_string_buffer(max(1, count * nsib * DIGEST_BYTES))
+
+    def _openings(self, rows, sib, count, nsib):
+        """open()'s result per index from the filled buffers"""
         raws, sraw, out = [r.raw for r in rows], sib.raw, []
         for q in range(count):
-            base = q * (n - 1)
+            base = q * nsib
             out.append(([r[q * c * WORD:(q + 1) * c * WORD] for r, c in zip(raws, self._cols)],
-                        [sraw[(base + k) * DIGEST_BYTES:(base + k + 1) * DIGEST_BYTES] for k in range(n - 1)]))
+                        [sraw[(base + k) * DIGEST_BYTES:(base + k + 1) * DIGEST_BYTES] for k in range(nsib)]))
         return out
 
     @property

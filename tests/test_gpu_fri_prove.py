@@ -15,7 +15,12 @@ Paths covered:
   gathers    trees with and without the bit-reversed flag, a height that is no
              power of two (rows that open as zeros), rows of 1, 5, 33 columns
              (part of a block's 256 lanes) and of 257 and 300 (a lane copies a
-             second column), every index, repeats, shuffled order
+             second column), every index, repeats, shuffled order; each
+             batched answer is compared with the single-index call, which is
+             the same kernel at count 1, and with poseidon2_ref / fri_ref
+  count 1    the single-index calls as batches of one: the edges of the index
+             range, launch counts, refusals that leave the caller's buffers
+             alone, an opening without a commit-phase tree, a one-leaf tree
   the proof  the reference unit test's shapes (duplicate query indices occur)
              and a two-round, four-matrix shape with two points, no point, 33
              queries and 12 bits
@@ -227,12 +232,15 @@ def test_open_batch_equals_open(case):
     tree = FieldMerkleTree("horizen")
     assert tree.build([(stored(m), r, c) for m, (r, c) in zip(mats, dims)], bit_reversed=flag)
     root = canon(tree.root)
-    assert (root == R.build(mats, "horizen", bit_reversed=flag)[-1][0]).all()
+    layers = R.build(mats, "horizen", bit_reversed=flag)
+    assert (root == layers[-1][0]).all()
     indices = batch_indices(32, 4401)
     got = tree.open_batch(indices)
     assert got is not None and len(got) == len(indices)
     for index, (rows, sibs) in zip(indices, got):
         assert (rows, sibs) == tree.open(index), index
+        wrows, wsibs = R.open_at(mats, layers, index, bit_reversed=flag)
+        assert rows == [stored(w) for w in wrows] and sibs == [stored(s) for s in wsibs], index
         if case == "plain_24_6" and index >= 24:
             assert all(r == bytes(len(r)) for r in rows)     # rows past the heights open as zeros
         assert verify_padded(root, dims, index, [canon(r) for r in rows], [canon(s) for s in sibs], "horizen"), index
@@ -263,21 +271,36 @@ ALPHA = F.ext(1234567, 7654321, 1111111, 2013265920)
 ZETA = F.ext(987654321, 5, 2013265920, 42)
 
 
-@pytest.mark.parametrize("log_blowup", [1, 2])
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "_".join("".join(map(str, r)) for r in s))
-def test_answer_queries_equals_answer_query(shape, log_blowup):
+def ended_opening(shape, log_blowup):
+    """An opening of random matrices of 5 columns, one point each, taken to the
+    end of its commit phase, and fri_ref's answer_query for the same inputs."""
     from tachyon_amd.fri import FriOpening
     fri = FriOpening(log_blowup)
     assert fri.begin(F.to_bytes(ALPHA))
+    rounds = []
     for r, degs in enumerate(shape):
-        mats = []
-        for m, d in enumerate(degs):
-            n = 1 << (d + log_blowup)
-            mats.append((stored(rand_words(4500 + 10 * r + m, n * 5)), n, 5))
-        assert fri.add_round(mats, [[F.to_bytes(ZETA)]] * len(mats)) is not None
+        mats = [rand_words(4500 + 10 * r + m, (5 << (d + log_blowup))).reshape(-1, 5) for m, d in enumerate(degs)]
+        rounds.append((mats, [[ZETA]] * len(mats)))
+        assert fri.add_round([(stored(m), m.shape[0], 5) for m in mats], [[F.to_bytes(ZETA)]] * len(mats)) is not None
     assert fri.answer_queries([0]) is None                   # before the phase has ended
     k = iter(range(100))
-    fri.commit_phase(lambda root: F.to_bytes(F.ext(3 + next(k), 5, 7, 11)))
+    roots = fri.commit_phase(lambda root: F.to_bytes(F.ext(3 + next(k), 5, 7, 11)))
+    _, ro = F.reduce_openings(ALPHA, rounds, log_blowup)
+    k = iter(range(100))
+    want_roots, trees, vectors, _ = F.commit_phase([ro[lg] for lg in sorted(ro, reverse=True)], log_blowup,
+                                                   lambda root: F.ext(3 + next(k), 5, 7, 11))
+    assert roots == [stored(r) for r in want_roots]
+
+    def want(index):
+        return [(F.to_bytes(val), [stored(s) for s in sibs]) for val, sibs in F.answer_query(index, trees, vectors)]
+
+    return fri, want
+
+
+@pytest.mark.parametrize("log_blowup", [1, 2])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "_".join("".join(map(str, r)) for r in s))
+def test_answer_queries_equals_answer_query(shape, log_blowup):
+    fri, want = ended_opening(shape, log_blowup)
     n = 1 << fri.input_log_size(0)
     indices = batch_indices(n, 4501)
     got = fri.answer_queries(indices)
@@ -286,6 +309,7 @@ def test_answer_queries_equals_answer_query(shape, log_blowup):
         assert fri.last_launches == 1                        # one launch for every query and tree
     for index, ans in zip(indices, got):
         assert ans == fri.answer_query(index), index
+        assert ans == want(index), index
     assert fri.answer_queries([]) is None and fri.answer_queries([0, n]) is None
     assert fri.answer_queries(list(range(n)) * ((1 << 16) // n) + [0]) is None      # above 2^16
     fri.close()
@@ -618,3 +642,127 @@ def test_cpp_client_prove(external):
     assert r.returncode == 0, r.stdout + r.stderr
     got = json.loads(r.stdout)
     assert got["ok"] is True and got["commits"] == log_rows and got["queries"] == queries
+
+
+# ---- 9. a single index is a batch of one
+def test_answer_query_is_answer_queries_at_one_index():
+    """log_blowup 1, inputs at log heights 5 and 3: the first, an inner and the
+    last index against fri_ref, one launch each; the first index out of range is
+    refused by both calls, which leave the caller's buffers alone"""
+    from tachyon_amd._lib import lib
+    fri, want = ended_opening(((4, 2),), 1)
+    assert fri.input_log_size(0) == 5 and fri.input_log_size(1) == 3 and fri.num_commits == 4
+    for index in (0, 13, 31):
+        single = fri.answer_query(index)
+        assert fri.last_launches == 1
+        assert single == want(index), index
+        batch = fri.answer_queries([index])
+        assert fri.last_launches == 1
+        assert batch == [single], index
+    assert fri.answer_query(32) is None and fri.answer_queries([32]) is None
+    vals = ctypes.create_string_buffer(b"\xaa" * (4 * 16), 4 * 16)
+    sibs = ctypes.create_string_buffer(b"\xaa" * (10 * 32), 10 * 32)           # 4 + 3 + 2 + 1 digests
+    idx = (ctypes.c_size_t * 1)(32)
+    assert lib().tachyon_mi355x_baby_bear_fri_opening_answer_query(fri._h, 32, vals, sibs) == 0
+    assert lib().tachyon_mi355x_baby_bear_fri_opening_answer_queries(fri._h, idx, 1, vals, sibs) == 0
+    assert vals.raw == b"\xaa" * len(vals.raw) and sibs.raw == b"\xaa" * len(sibs.raw)
+    assert lib().tachyon_mi355x_baby_bear_fri_opening_answer_query(fri._h, 31, vals, sibs) == 1
+    assert _split(vals.raw, sibs.raw, 5, 4) == want(31)
+    fri.close()
+
+
+def _split(vals: bytes, sibs: bytes, log_max: int, commits: int):
+    out, at = [], 0
+    for i in range(commits):
+        n = log_max - i - 1
+        out.append((vals[16 * i:16 * (i + 1)], [sibs[32 * (at + k):32 * (at + k + 1)] for k in range(n)]))
+        at += n
+    return out
+
+
+@pytest.mark.parametrize("log_blowup", [1, 2])
+def test_answer_query_without_a_commit_phase_tree(log_blowup):
+    """The largest input has log height log_blowup: nothing is committed.  The
+    single call answers without looking at its output pointers; the batched one
+    wants its first array, and neither writes."""
+    from tachyon_amd._lib import lib
+    L = lib()
+    fri, want = ended_opening(((0,),), log_blowup)
+    n = 1 << log_blowup
+    assert fri.num_commits == 0 and fri.input_log_size(0) == log_blowup
+    buf = ctypes.create_string_buffer(b"\xaa" * 64, 64)
+    idx = (ctypes.c_size_t * 2)(n - 1, 0)
+    assert L.tachyon_mi355x_baby_bear_fri_opening_answer_query(fri._h, n - 1, None, None) == 1
+    assert L.tachyon_mi355x_baby_bear_fri_opening_answer_query(fri._h, n - 1, buf, None) == 1
+    assert L.tachyon_mi355x_baby_bear_fri_opening_answer_query(fri._h, n, None, None) == 0
+    assert L.tachyon_mi355x_baby_bear_fri_opening_answer_queries(fri._h, idx, 2, buf, None) == 1
+    assert L.tachyon_mi355x_baby_bear_fri_opening_answer_queries(fri._h, idx, 2, None, None) == 0
+    idx[1] = n
+    assert L.tachyon_mi355x_baby_bear_fri_opening_answer_queries(fri._h, idx, 2, buf, None) == 0
+    assert buf.raw == b"\xaa" * 64
+    assert fri.answer_query(n - 1) == [] == want(n - 1) and fri.answer_queries([0, n - 1]) == [[], []]
+    assert fri.answer_query(n) is None and fri.answer_queries([n]) is None
+    fri.close()
+
+
+# A tree takes no two heights that round up to the same power of two, and the
+# bit-reversed flag takes powers of two only, so the 32-row matrices and the
+# 30-row one cannot share a tree: the 30-row matrix stands with a short one.
+ONE_INDEX_TREES = {"natural_32_32": ([(32, 5), (32, 3)], False), "bit_reversed_32_32": ([(32, 5), (32, 3)], True),
+                   "natural_30_4": ([(30, 7), (4, 2)], False)}
+
+
+@pytest.mark.parametrize("case", list(ONE_INDEX_TREES))
+def test_open_is_open_batch_at_one_index(case):
+    from tachyon_amd.poseidon2 import FieldMerkleTree
+    dims, flag = ONE_INDEX_TREES[case]
+    mats = [rand_words(4700 + i, r * c).reshape(r, c) for i, (r, c) in enumerate(dims)]
+    tree = FieldMerkleTree("horizen")
+    assert tree.build([(stored(m), r, c) for m, (r, c) in zip(mats, dims)], bit_reversed=flag)
+    launches = tree.last_launches
+    layers = R.build(mats, "horizen", bit_reversed=flag)
+    assert (canon(tree.root) == layers[-1][0]).all()
+    for index in (0, 29, 30, 31):
+        wrows, wsibs = R.open_at(mats, layers, index, bit_reversed=flag)
+        want = ([stored(w) for w in wrows], [stored(s) for s in wsibs])
+        assert tree.open(index) == want, index
+        assert tree.open_batch([index]) == [want], index
+        assert tree.last_launches == launches
+        if dims[0][0] == 30 and index >= 30:                 # past 30 rows: zeros; row 3 of 4 is there
+            assert want[0][0] == bytes(4 * 7) and want[0][1] != bytes(4 * 2)
+    assert tree.open(32) is None and tree.open_batch([32]) is None
+    if not flag:                                             # what keeps 32 and 30 rows out of one tree
+        both = [(32, 5), (30, 7)]
+        assert not tree.build([(bytes(4 * r * c), r, c) for r, c in both])
+        assert not tree.build([(bytes(4 * 30 * 7), 30, 7)], bit_reversed=True)
+        assert tree.open(31) == want                         # a refused build leaves the tree as it was
+    tree.close()
+
+
+def test_open_on_a_one_leaf_tree():
+    """one matrix of one row: the root is the leaf's hash, there are no
+    siblings, and open wants no siblings_out"""
+    from tachyon_amd._lib import lib
+    from tachyon_amd.poseidon2 import FieldMerkleTree
+    L = lib()
+    mat = rand_words(4800, 6).reshape(1, 6)
+    tree = FieldMerkleTree("horizen")
+    assert tree.build([(stored(mat), 1, 6)])
+    launches = tree.last_launches
+    layers = R.build([mat], "horizen")
+    assert len(layers) == 1 and (canon(tree.root) == layers[0][0]).all()
+    row = ctypes.create_string_buffer(b"\xaa" * 24, 24)
+    ptrs = (ctypes.c_void_p * 1)(ctypes.addressof(row))
+    idx = (ctypes.c_size_t * 1)(0)
+    assert L.tachyon_mi355x_baby_bear_merkle_tree_open(tree._h, 0, ptrs, None) == 1 and row.raw == stored(mat)
+    row.raw = b"\xaa" * 24
+    assert L.tachyon_mi355x_baby_bear_merkle_tree_open_batch(tree._h, idx, 1, ptrs, None) == 1
+    assert row.raw == stored(mat)
+    row.raw = b"\xaa" * 24
+    idx[0] = 1
+    assert L.tachyon_mi355x_baby_bear_merkle_tree_open(tree._h, 1, ptrs, None) == 0
+    assert L.tachyon_mi355x_baby_bear_merkle_tree_open_batch(tree._h, idx, 1, ptrs, None) == 0
+    assert row.raw == b"\xaa" * 24
+    assert tree.open(0) == ([stored(mat)], []) == tree.open_batch([0])[0] and tree.open(1) is None
+    assert tree.last_launches == launches
+    tree.close()

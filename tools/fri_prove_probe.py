@@ -217,8 +217,8 @@ def main():
     out["open_loop"] = timed(lambda: [tree.open(i) for i in spread])
     for k in ("answer_queries", "open_batch"):
         out[k].update({"launches": 1, "waits": 1})
-    out["answer_query_loop"].update({"launches": args.queries, "waits": args.queries})
-    out["open_loop"].update({"launches": 0, "waits": args.queries})
+    for k in ("answer_query_loop", "open_loop"):     # a batch of one per index
+        out[k].update({"launches": args.queries, "waits": args.queries})
 
     fri.close()
     tree.close()
