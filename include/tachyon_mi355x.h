@@ -899,7 +899,12 @@ TACHYON_C_EXPORT int tachyon_mi355x_msm_shard_plan(int curve, size_t n_total, in
  * and their group sum -- every rank writes the whole MSM's affine result and
  * returns 1.  A rank whose local part fails still enters the exchange with a
  * failure flag, so no rank is left waiting in the collective: then EVERY rank
- * returns 0 (out untouched, the message on stderr) instead of aborting. */
+ * returns 0 (out untouched, the message on stderr) instead of aborting.
+ * A plan that does not match the call fails the same way, before any local
+ * work: point_groups x window_groups != the communicator's world, w_begin >
+ * w_end, w_end above the window count of window_bits for the curve, a null
+ * plan or an unknown curve id (the exchanged record has one size on every
+ * curve, so such a rank still joins the all-gather). */
 TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_sharded_plan_affine(int curve, void* ctx, tachyon_mi355x_comm* comm,
                                                                 const tachyon_mi355x_msm_shard* plan,
                                                                 const void* bases, const void* scalars,
@@ -925,6 +930,16 @@ TACHYON_C_EXPORT void tachyon_mi355x_msm_gpu_last_timings(int curve, const void*
  * icicle_msm_utils.cc:10-68; TACHYON_MSM_MEM_LIMIT caps the free bytes) or when
  * host-resident inputs were uploaded chunk by chunk under the kernels. */
 TACHYON_C_EXPORT size_t tachyon_mi355x_msm_gpu_last_divisions(int curve, const void* ctx);
+/* Memory planning, read-only.  _run_bytes: the estimate (with its 10 % margin)
+ * of the device working set of a `size`-point run under the context's window
+ * bits and variant -- what the division into point chunks and the fold-table
+ * fit are decided from; with batch_count > 0 the estimate for a batch of
+ * batch_count MSMs of `size` points each (_batch_affine).  _held_bytes: the
+ * bytes of the working buffers the context holds now (grown by its runs, kept
+ * for the next).  With set_devices active both report the lead shard, as
+ * _last_schedule does.  0 for a null context. */
+TACHYON_C_EXPORT size_t tachyon_mi355x_msm_gpu_run_bytes(int curve, const void* ctx, size_t size, size_t batch_count);
+TACHYON_C_EXPORT size_t tachyon_mi355x_msm_gpu_held_bytes(int curve, const void* ctx);
 /* Schedule of the last run (of its last point chunk): bit 0 the recode fused
  * with the first radix pass, bit 1 onesweep passes fed by the recode's digit
  * counts, bit 2 7-byte LDS staging in the recode scatter, bit 3 an

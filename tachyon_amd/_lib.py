@@ -149,6 +149,8 @@ SIGNATURES = [
     ("tachyon_mi355x_msm_gpu_set_profile", None, [i32, vp, i32]),
     ("tachyon_mi355x_msm_gpu_set_variant", i32, [i32, vp, i32]),
     ("tachyon_mi355x_msm_gpu_last_divisions", sz, [i32, vp]),
+    ("tachyon_mi355x_msm_gpu_run_bytes", sz, [i32, vp, sz, sz]),
+    ("tachyon_mi355x_msm_gpu_held_bytes", sz, [i32, vp]),
     ("tachyon_mi355x_msm_gpu_last_schedule", ctypes.c_uint, [i32, vp]),
     ("tachyon_mi355x_msm_madd_ceiling", ctypes.c_double, [i32, i32]),
     ("tachyon_mi355x_msm_gpu_set_devices", i32, [i32, vp, ctypes.POINTER(ctypes.c_int), sz]),

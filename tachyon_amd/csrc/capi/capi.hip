@@ -246,31 +246,84 @@ void msm_sharded_out(void* ctx, dist::Comm* comm, const void* bases, const void*
   memcpy(out, &a, sizeof(a));
 }
 
+#define CURVE_DISPATCH(curve, CALL)                               \
+  switch (curve) {                                                \
+    case 0: { using C = Bn254G1; CALL; } break;                   \
+    case 1: { using C = Bn254G2; CALL; } break;                   \
+    case 2: { using C = Bls381G1; CALL; } break;                  \
+    case 3: { using C = Bls381G2; CALL; } break;                  \
+    default: throw std::runtime_error("unknown curve id");        \
+  }
+
 // One rank's part of a tachyon_mi355x_msm_shard plan: its point group over
 // its window range (the hybrid partition; a point shard when window_groups
 // is 1), the all-gather of the XYZZ partials and their sum in rank order.
 // The window-range partials sum_{w in range} 2^(c w) S_w of the Q ranges of
 // one point group add up to that group's MSM, the groups' to the whole MSM.
+// The exchanged record has one size on every curve (the largest XYZZ), so a
+// rank whose plan or curve id is bad can still enter the all-gather with its
+// failure flag: the plan is checked against the communicator and the curve's
+// window count inside gather_checked's local part, before any local work.
+struct ShardPartial {
+  alignas(8) uint8_t bytes[sizeof(XYZZ<Bls381G2::F>)];
+};
+
 template <class Curve>
-void msm_sharded_plan_out(void* ctx, dist::Comm* comm, const tachyon_mi355x_msm_shard& p, const void* bases,
-                          const void* scalars, void* out) {
+ShardPartial msm_shard_partial(void* ctx, dist::Comm* comm, const tachyon_mi355x_msm_shard& p, const void* bases,
+                               const void* scalars) {
   using F = typename Curve::F;
+  static_assert(sizeof(XYZZ<F>) <= sizeof(ShardPartial));
   auto* c = static_cast<MsmCtx<Curve>*>(ctx);
-  const std::vector<XYZZ<F>> all = dist::gather_checked<XYZZ<F>>(comm, [&]() -> XYZZ<F> {
-    if (!c) throw std::runtime_error("null MSM context");
-    if (p.window_groups <= 1) return c->run(bases, scalars, p.count);
+  if ((uint64_t)p.point_groups * p.window_groups != (uint64_t)comm->world())
+    throw std::runtime_error("shard plan of " + std::to_string(p.point_groups) + " x " +
+                             std::to_string(p.window_groups) + " ranks on a communicator of " +
+                             std::to_string(comm->world()));
+  if (p.w_begin > p.w_end) throw std::runtime_error("shard plan with w_begin > w_end");
+  if (p.window_bits > 26) throw std::runtime_error("shard plan with more than 26 window bits");
+  if (!c) throw std::runtime_error("null MSM context");
+  const unsigned bits = p.window_bits ? p.window_bits : c->impl.force_window_bits();
+  const unsigned W = msm::MsmPlan::make(p.count, Curve::Fr::Config::kModulusBits, bits).windows;
+  if (p.w_end > W)
+    throw std::runtime_error("shard plan with w_end " + std::to_string(p.w_end) + " above the " + std::to_string(W) +
+                             " windows of its window bits");
+  XYZZ<F> part;
+  if (p.window_groups <= 1) {
+    part = c->run(bases, scalars, p.count);
+  } else {
     struct Restore {
       msm::MsmGpu<Curve>& m;
       unsigned c;
       ~Restore() { m.set_force_window_bits(c); }
     } restore{c->impl, c->impl.force_window_bits()};
     c->impl.set_force_window_bits(p.window_bits);
-    return c->impl.run_window_range(bases, scalars, p.count, p.w_begin, p.w_end);
-  });
+    part = c->impl.run_window_range(bases, scalars, p.count, p.w_begin, p.w_end);
+  }
+  ShardPartial out{};
+  memcpy(out.bytes, &part, sizeof(part));
+  return out;
+}
+
+template <class Curve>
+void msm_shard_sum(const std::vector<ShardPartial>& all, void* out) {
+  using F = typename Curve::F;
   XYZZ<F> acc = XYZZ<F>::zero();
-  for (const auto& q : all) acc = acc + q;
+  for (const ShardPartial& q : all) {
+    XYZZ<F> v;
+    memcpy(&v, q.bytes, sizeof(v));
+    acc = acc + v;
+  }
   const Affine<F> a = acc.to_affine();
   memcpy(out, &a, sizeof(a));
+}
+
+void msm_sharded_plan_out(int curve, void* ctx, dist::Comm* comm, const tachyon_mi355x_msm_shard* plan,
+                          const void* bases, const void* scalars, void* out) {
+  const std::vector<ShardPartial> all = dist::gather_checked<ShardPartial>(comm, [&]() -> ShardPartial {
+    if (!plan) throw std::runtime_error("null shard plan");
+    CURVE_DISPATCH(curve, return msm_shard_partial<C>(ctx, comm, *plan, bases, scalars))
+    return ShardPartial{};
+  });
+  CURVE_DISPATCH(curve, msm_shard_sum<C>(all, out))
 }
 
 // The hybrid point x window partitions (curve id, world) -> (window groups Q,
@@ -441,15 +494,6 @@ tachyon_bls12_381_g2_jacobian* tachyon_bls12_381_g2_affine_msm_gpu(tachyon_bls12
 }
 
 // ---- curve-generic extensions ----
-#define CURVE_DISPATCH(curve, CALL)                               \
-  switch (curve) {                                                \
-    case 0: { using C = Bn254G1; CALL; } break;                   \
-    case 1: { using C = Bn254G2; CALL; } break;                   \
-    case 2: { using C = Bls381G1; CALL; } break;                  \
-    case 3: { using C = Bls381G2; CALL; } break;                  \
-    default: throw std::runtime_error("unknown curve id");        \
-  }
-
 void tachyon_mi355x_msm_gpu_affine(int curve, void* ctx, const void* bases, const void* scalars, size_t size,
                                    void* out_affine) {
   GUARD_BEGIN CURVE_DISPATCH(curve, msm_affine_out<C>(ctx, bases, scalars, size, out_affine)) GUARD_END
@@ -540,8 +584,9 @@ int tachyon_mi355x_msm_gpu_sharded_plan_affine(int curve, void* ctx, tachyon_mi3
   // the exchange, and every rank returns 0 with the message on stderr)
   try {
     if (!comm || !comm->impl) throw std::runtime_error("null communicator");
-    if (!plan) throw std::runtime_error("null shard plan");
-    CURVE_DISPATCH(curve, msm_sharded_plan_out<C>(ctx, comm->impl.get(), *plan, bases, scalars, out_affine))
+    // (a null plan, a bad curve id and a plan that does not match the
+    // communicator fail inside the exchange, where every rank sees them)
+    msm_sharded_plan_out(curve, ctx, comm->impl.get(), plan, bases, scalars, out_affine);
     return 1;
   } catch (const std::exception& e) {
     fprintf(stderr, "[tachyon_mi355x] %s failed: %s\n", __func__, e.what());
@@ -638,6 +683,23 @@ size_t tachyon_mi355x_msm_gpu_last_divisions(int curve, const void* ctx) {
   GUARD_BEGIN CURVE_DISPATCH(curve, {
     auto* m = static_cast<const MsmCtx<C>*>(ctx);
     return m->multi ? m->multi->last_divisions() : m->impl.last_divisions();
+  }) GUARD_END
+  return 0;
+}
+size_t tachyon_mi355x_msm_gpu_run_bytes(int curve, const void* ctx, size_t size, size_t batch_count) {
+  if (!ctx) return 0;
+  GUARD_BEGIN CURVE_DISPATCH(curve, {
+    auto* m = static_cast<const MsmCtx<C>*>(ctx);
+    const msm::MsmGpu<C>& g = m->multi ? m->multi->lead() : m->impl;
+    return batch_count ? g.batch_run_bytes(size, batch_count) : g.run_bytes(size);
+  }) GUARD_END
+  return 0;
+}
+size_t tachyon_mi355x_msm_gpu_held_bytes(int curve, const void* ctx) {
+  if (!ctx) return 0;
+  GUARD_BEGIN CURVE_DISPATCH(curve, {
+    auto* m = static_cast<const MsmCtx<C>*>(ctx);
+    return m->multi ? m->multi->lead().held_bytes() : m->impl.held_bytes();
   }) GUARD_END
   return 0;
 }

@@ -224,9 +224,13 @@ class MsmGpu {
   //    build staging and the run's working set fit device_budget() +
   //    `reusable` (an older table the caller will drop), with fold x points <
   //    2^31 base indices; 1 = no table (run / run_groups instead).
+  //  * held_bytes: the working buffers this context holds now.
   size_t device_budget() const;
+  size_t held_bytes() const;
   size_t run_bytes(size_t n) const { return work_bytes(n, force_c_); }
-  size_t batch_run_bytes(size_t len, size_t count) const { return work_bytes(len * count, batch_window_bits(len)); }
+  size_t batch_run_bytes(size_t len, size_t count) const {
+    return work_bytes(len * count, batch_window_bits(len), std::max<size_t>(1, count));
+  }
   unsigned fit_fold(size_t points, unsigned windows, unsigned want, size_t run_bytes, size_t reusable = 0) const;
   static size_t fold_table_bytes(size_t points, unsigned fold) { return (size_t)fold * points * sizeof(Aff); }
   // staging of fold_bases: XYZZ copies + Montgomery-trick prefixes of one
@@ -274,8 +278,39 @@ class MsmGpu {
   void fold_bases_c(const void* bases, size_t n, unsigned fold, void* out, unsigned c);
   void enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, const MsmPlan& plan, Point* d_windows);
   Point run_host_pipelined(const void* bases, const void* scalars, size_t n, size_t chunks);
-  size_t work_bytes(size_t n, unsigned c) const;
-  size_t held_bytes() const;
+  size_t work_bytes(size_t n, unsigned c, size_t batch = 1) const;
+  // The plan of an n-point run under this context's variant bits (run_windows
+  // and work_bytes: one rule for both).
+  MsmPlan run_plan(size_t n, unsigned c) const;
+  // The field code the variant bits select (run_windows sets the members of
+  // the same names from it; work_bytes reads it before any run has).
+  struct AccFields {
+    bool tree_reduce, acc29, acc28, pair_acc, pair_limb;
+  };
+  static AccFields acc_fields(int variant);
+  // Bytes of one bucket sum / piece (`slot`) and of one join-level entry
+  // (`lvl_slot`), and whether they are raw limbs -- the one rule enqueue
+  // allocates by and work_bytes estimates by.
+  struct SlotBytes {
+    size_t slot, lvl_slot;
+    bool raw;
+  };
+  static SlotBytes slot_bytes(const AccFields& f, int variant);
+  static bool window_sums_by_scan(const AccFields& f, unsigned buckets);  // no segment sums then
+  // The sort of a run's entries (enqueue) and what its scratch takes
+  // (work_bytes): the recode knobs of the variant bits, then the shape.
+  struct SortKnobs {
+    bool fuse_recode, rocprim_hist, wide_stage;
+    uint32_t spt;
+  };
+  static SortKnobs sort_knobs(int variant);
+  struct SortShape {
+    unsigned key_bits, sort_begin, places;
+    uint32_t spt;
+    bool narrow, fused, own_sort;
+    size_t scatter_lds;
+  };
+  static SortShape sort_shape(const SortKnobs& k, unsigned c, unsigned Ws, unsigned W, unsigned G, size_t entries);
   size_t memory_divisions(size_t n, size_t resident_bytes) const;
   void ensure_group_events(unsigned groups);
   void build_chains(const uint32_t* flags, const uint32_t* last, size_t T, unsigned K2, uint32_t* is_start,

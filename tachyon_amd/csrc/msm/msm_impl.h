@@ -797,7 +797,8 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 //      ahead -- a line per two entries (FETCH 93.7 B per entry; 2^26
 //      accumulation 59.6 -> 58.9 ms, profiles/r06h/ab_ent_pairs.log)
 //   2: 64-byte chunks (8 entries) through LDS by LDS-DMA, the next chunk
-//      8 iterations ahead, double-buffered: 4 KiB per wave, no VGPRs; the
+//      8 iterations ahead, double-buffered: 8 KiB of LDS per wave (4 KiB per
+//      buffer), 32 KiB per 256-thread workgroup, no VGPRs; the
 //      lane's first entry must be 16-byte aligned (g0 even: gbeg and K even)
 //      and the entry array 64 bytes longer than gend (MsmGpu::enqueue's
 //      slack).  FETCH 72.4 B per entry = the 64-byte base + 8; 2^26
@@ -2419,30 +2420,11 @@ void MsmGpu<Curve>::enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, c
   // (64 bytes of slack: the LDS-staged entry chunks read up to 7 entries past a lane's last)
   uint64_t* ents = static_cast<uint64_t*>(ents_.ensure(entries * 8 + 64));
   uint64_t* ents2 = static_cast<uint64_t*>(ents2_.ensure(entries * 8 + 64));
-  // bucket sums and pieces in the 144-byte Raw format after the 29-bit
-  // accumulation (not with the workgroup-tree window sums, an A/B path in R form)
-  // (BLS12-381 G1: 224-byte Pol28::Raw after the 28-bit accumulation, read by
-  // the 28-bit reductions -- not with the FIPS reductions of bit 22 or the
-  // two-level window sums of bit 23; every join level raw, so the level buffer
-  // takes the raw slot too)
-  bool raw = false;
-  size_t slot = sizeof(Point), lvl_slot = sizeof(Point);
-  if constexpr (std::is_same_v<Curve, Bn254G1>) {
-    raw = acc29_ && !tree_reduce_;
-    if (raw) slot = sizeof(acc29::Raw);
-  }
-  if constexpr (std::is_same_v<Curve, Bls381G1>) {
-    raw = acc28_ && !tree_reduce_ && !(variant_ & ((1 << 22) | (1 << 23)));
-    if (raw) slot = lvl_slot = sizeof(Pol28::Raw);
-  }
-  // (G2 lane pairs over the limb fields: 8 raw components per point -- 448 B
-  // BLS12-381, 288 B BN254 -- not with the FIPS pair reductions (bit 22), the
-  // two-level (bit 23) or two-pass (bit 24) window sums)
-  if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>) {
-    using LimbPol = std::conditional_t<std::is_same_v<Curve, Bls381G2>, PairPol28, PairPol29>;
-    raw = pair_acc_ && pair_limb_ && !tree_reduce_ && !(variant_ & ((1 << 22) | (1 << 23) | (1 << 24)));
-    if (raw) slot = lvl_slot = 8 * sizeof(typename LimbPol::F);
-  }
+  // bucket sums, pieces and join levels in the accumulation's raw limb format
+  // where the reductions read it (slot_bytes; work_bytes estimates by the same rule)
+  const SlotBytes sb = slot_bytes({tree_reduce_, acc29_, acc28_, pair_acc_, pair_limb_}, variant_);
+  const bool raw = sb.raw;
+  const size_t slot = sb.slot, lvl_slot = sb.lvl_slot;
   Point* bucket_sum = static_cast<Point*>(buckets_.ensure(nb * slot));
   Point* pieces = static_cast<Point*>(part_a_.ensure(2 * T * slot));
   Point* lvl_buf = static_cast<Point*>(part_b_.ensure((2 * T / kJoinFanLong + T + 2) * lvl_slot));
@@ -2486,21 +2468,12 @@ void MsmGpu<Curve>::enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, c
   uint32_t* lcnt = ctab + 3 * (T + 2);
   uint32_t* dscal = ctab + 6 * (T + 2);  // [0] nchains, [1] max chain length
 
-  unsigned wbits = 0;
-  while ((1u << wbits) < W) ++wbits;
-  const unsigned key_bits = (G == 1) ? c : c + wbits;  // the window bits only matter within a multi-window group
-  // recode fused with the first (low byte) radix pass; one sort group only
-  // (the scatter stages a block's spt x 256 x W entries in LDS, <= 128 KiB)
-  const uint32_t spt = recode_spt_;
-  const bool narrow = key_bits <= 24 && !wide_stage_;  // 7-byte LDS staging in the scatter
-  const size_t scatter_lds = (size_t)spt * kBlock * Ws * (narrow ? 7 : sizeof(uint64_t));
-  const bool fused = fuse_recode_ && G == W && scatter_lds <= 128 * 1024;
-  const unsigned sort_begin = fused ? std::min(8u, key_bits) : 0u;
-  // onesweep passes fed with digit counts from the recode (places = the
-  // 8-bit digits after the fused low byte); rocPRIM's radix_sort_keys
-  // otherwise (set_variant bit 10, or other tile shapes, or > 2 places)
-  const unsigned places = (key_bits - sort_begin + 7) / 8;
-  const bool own_sort = fused && !rocprim_hist_ && places <= 2 && entries < (size_t(1) << 32);
+  // the sort's shape (sort_shape: work_bytes sizes the sort scratch by the same rule)
+  const SortShape ss = sort_shape({fuse_recode_, rocprim_hist_, wide_stage_, recode_spt_}, c, Ws, W, G, entries);
+  const unsigned key_bits = ss.key_bits, sort_begin = ss.sort_begin, places = ss.places;
+  const uint32_t spt = ss.spt;
+  const bool narrow = ss.narrow, fused = ss.fused, own_sort = ss.own_sort;
+  const size_t scatter_lds = ss.scatter_lds;
   last_schedule_ = (fused ? kSchedFusedRecode : 0u) | (own_sort ? kSchedRecodeFedSort : 0u) |
                    (fused && narrow ? kSchedNarrowStaging : 0u);
   uint32_t* digit_off = nullptr;
@@ -2961,7 +2934,7 @@ void MsmGpu<Curve>::enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, c
   bool tree29 = false;
   if constexpr (std::is_same_v<Curve, Bn254G1>) {
     tree29 = acc29_;
-    if (tree29 && B <= kBlock) {
+    if (window_sums_by_scan({tree_reduce_, acc29_, acc28_, pair_acc_, pair_limb_}, B)) {
       auto* scan = raw ? &window_scan29_kernel<true> : &window_scan29_kernel<false>;
       hipLaunchKernelGGL(scan, dim3(W), dim3(kBlock), 0, stream_, bucket_sum, B, d_windows);
       TA_HIP(hipGetLastError());
@@ -3022,60 +2995,25 @@ void MsmGpu<Curve>::enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, c
 template <class Curve>
 void MsmGpu<Curve>::run_windows(const void* bases, const void* scalars, size_t n, std::vector<Point>* out,
                                 MsmPlan* plan_out) {
-  MsmPlan plan = MsmPlan::make(n, Fr::Config::kModulusBits, force_c_, range_begin_, range_end_);
-  // G2: running-sum segments twice the G1 rule's length -- a G2 fix-up costs
-  // more against the latency-bound loop (BLS12-381 G2 2^24 reduction 13.7 ->
-  // 13.0 ms at L = 128, BN254 G2 2^22 1.75 -> 1.64 ms at L = 32;
-  // profiles/r05am, r05an)
-  if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>) {
-#ifdef TACHYON_TUNING_KNOBS
-    if (!getenv("TACHYON_MSM_SEG"))
-#endif
-      plan.seg = std::min(plan.buckets, std::min(128u, plan.seg * 2));
-  }
-  switch (variant_ & 3) {  // accumulation chunk experiments
-    case 1: plan.K = std::min(2048u, plan.K * 2); break;
-    case 2: plan.K = std::min(2048u, plan.K * 4); break;
-    case 3: plan.K = std::max(4u, plan.K / 2); break;
-    default: break;
-  }
-  switch ((variant_ >> 2) & 3) {  // windows per sort/accumulate group
-    case 1: plan.group = 1; break;
-    case 2: plan.group = 2; break;
-    case 3: plan.group = plan.active(); break;
-    default: break;
-  }
+  MsmPlan plan = run_plan(n, force_c_);
   idx_mask_ = ~kSignBit;
-  fuse_recode_ = !(variant_ & 128);  // bit 7: the separate recode + full sort (A/B)
-  static constexpr uint32_t kSpt[] = {kRecodeSpt, 1, 4, 3};
-  recode_spt_ = kSpt[(variant_ >> 8) & 3];  // bits 8-9: scalars per thread of the fused recode
+  const SortKnobs sk = sort_knobs(variant_);
+  fuse_recode_ = sk.fuse_recode;
+  recode_spt_ = sk.spt;
   sort_cfg_ = (variant_ >> 4) & 3;  // bits 4-5: onesweep tile shape
 #ifdef TACHYON_TUNING_KNOBS
   if (const char* e = getenv("TACHYON_ONESWEEP_CFG")) sort_cfg_ = (unsigned)std::clamp(atoi(e), 0, 5);
 #endif
-  rocprim_hist_ = (variant_ & 1024) != 0;  // bit 10: rocPRIM's own digit histogram pass (A/B)
-  wide_stage_ = (variant_ & 2048) != 0;    // bit 11: 8-byte LDS staging in the recode scatter (A/B)
-  tree_reduce_ = (variant_ & 4096) != 0;   // bit 12: window sums by workgroup trees (A/B)
-  // BN254 G1 accumulates over the 29-bit-limb field with hand-chained products
-  // (field/f29_asm.h) and product-free conversions, the next base not
-  // prefetched (3 waves per SIMD): 2^26 accumulation 67.3 -> 61.0 ms, faster
-  // at every size from 2^16 (profiles/r03b/ab_acc29_conv.log).  Bit 18 forces
-  // the 32-bit FIPS field; bits 13 / 17 prefetch the next base in registers
-  // (2 waves) / through LDS by LDS-DMA (A/B); bit 14 is the default
-  const bool acc29_default = std::is_same_v<Curve, Bn254G1>;
-  acc29_ = !(variant_ & 262144) && ((variant_ & (8192 | 16384 | 131072)) != 0 || acc29_default);
+  rocprim_hist_ = sk.rocprim_hist;
+  wide_stage_ = sk.wide_stage;
+  // (what the variant bits select: acc_fields)
+  const AccFields af = acc_fields(variant_);
+  tree_reduce_ = af.tree_reduce;
+  acc29_ = af.acc29;
   acc29_mode_ = (variant_ & 131072) ? 2 : (variant_ & 8192) ? 1 : 0;
-  // BLS12-381 G1: the accumulation over 14 x 28-bit limbs (field/f28.h) by
-  // default; bit 20 restores the 12 x 32-bit FIPS field (A/B)
-  acc28_ = std::is_same_v<Curve, Bls381G1> && !(variant_ & (1 << 20));
-  // G2: the lane pair over the 28-bit (BLS12-381, msm/pair28.h) / 29-bit
-  // (BN254, msm/pair29.h) field; bit 20 restores the FIPS pair, bit 15 the
-  // one-lane FIPS kernel
-  pair_limb_ = (std::is_same_v<Curve, Bls381G2> || std::is_same_v<Curve, Bn254G2>) && !(variant_ & (1 << 20));
-  // G2: a lane pair per point with inline products by default (BLS12-381 G2
-  // 2^24 accumulation 129 -> 113 ms, BN254 G2 2^22 16.3 -> 15.7 ms); bit 15
-  // restores the one-lane kernel, bit 16 the pair with out-of-line 12-limb products
-  pair_acc_ = !(variant_ & 32768);
+  acc28_ = af.acc28;
+  pair_limb_ = af.pair_limb;
+  pair_acc_ = af.pair_acc;
   pair_inline_ = !(variant_ & 65536);
   if (plan_out) *plan_out = plan;
   if (fold_ > 1 && (plan.w_begin != 0 || plan.w_end != plan.windows || plan.windows % fold_ != 0))
@@ -3360,22 +3298,158 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::run_host_pipelined(const void* base
   return total;
 }
 
+// BN254 G1 over the 29-bit field with at most kBlock buckets per window: the
+// window sums are one scan launch per window, with no segment sums (enqueue;
+// work_bytes leaves them out of the estimate)
+template <class Curve>
+bool MsmGpu<Curve>::window_sums_by_scan(const AccFields& f, unsigned buckets) {
+  return std::is_same_v<Curve, Bn254G1> && f.acc29 && !f.tree_reduce && buckets <= detail::kBlock;
+}
+
+// The plan run_windows runs n points by: MsmPlan::make for the context's
+// window range, then the variant bits that change it.
+template <class Curve>
+MsmPlan MsmGpu<Curve>::run_plan(size_t n, unsigned c) const {
+  MsmPlan plan = MsmPlan::make(n, Fr::Config::kModulusBits, c, range_begin_, range_end_);
+  // G2: running-sum segments twice the G1 rule's length -- a G2 fix-up costs
+  // more against the latency-bound loop (BLS12-381 G2 2^24 reduction 13.7 ->
+  // 13.0 ms at L = 128, BN254 G2 2^22 1.75 -> 1.64 ms at L = 32;
+  // profiles/r05am, r05an)
+  if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>) {
+#ifdef TACHYON_TUNING_KNOBS
+    if (!getenv("TACHYON_MSM_SEG"))
+#endif
+      plan.seg = std::min(plan.buckets, std::min(128u, plan.seg * 2));
+  }
+  switch (variant_ & 3) {  // accumulation chunk experiments
+    case 1: plan.K = std::min(2048u, plan.K * 2); break;
+    case 2: plan.K = std::min(2048u, plan.K * 4); break;
+    case 3: plan.K = std::max(4u, plan.K / 2); break;
+    default: break;
+  }
+  switch ((variant_ >> 2) & 3) {  // windows per sort/accumulate group
+    case 1: plan.group = 1; break;
+    case 2: plan.group = 2; break;
+    case 3: plan.group = plan.active(); break;
+    default: break;
+  }
+  return plan;
+}
+
+template <class Curve>
+typename MsmGpu<Curve>::SortKnobs MsmGpu<Curve>::sort_knobs(int variant) {
+  SortKnobs k;
+  k.fuse_recode = !(variant & 128);  // bit 7: the separate recode + full sort (A/B)
+  static constexpr uint32_t kSpt[] = {detail::kRecodeSpt, 1, 4, 3};
+  k.spt = kSpt[(variant >> 8) & 3];  // bits 8-9: scalars per thread of the fused recode
+  k.rocprim_hist = (variant & 1024) != 0;  // bit 10: rocPRIM's own digit histogram pass (A/B)
+  k.wide_stage = (variant & 2048) != 0;    // bit 11: 8-byte LDS staging in the recode scatter (A/B)
+  return k;
+}
+
+// How the entries of a run are sorted: c window bits, Ws windows per scalar,
+// W key windows in groups of G, `entries` in all.
+template <class Curve>
+typename MsmGpu<Curve>::SortShape MsmGpu<Curve>::sort_shape(const SortKnobs& k, unsigned c, unsigned Ws, unsigned W,
+                                                            unsigned G, size_t entries) {
+  SortShape s;
+  unsigned wbits = 0;
+  while ((1u << wbits) < W) ++wbits;
+  s.key_bits = (G == 1) ? c : c + wbits;  // the window bits only matter within a multi-window group
+  // recode fused with the first (low byte) radix pass; one sort group only
+  // (the scatter stages a block's spt x 256 x W entries in LDS, <= 128 KiB)
+  s.spt = k.spt;
+  s.narrow = s.key_bits <= 24 && !k.wide_stage;  // 7-byte LDS staging in the scatter
+  s.scatter_lds = (size_t)s.spt * detail::kBlock * Ws * (s.narrow ? 7 : sizeof(uint64_t));
+  s.fused = k.fuse_recode && G == W && s.scatter_lds <= 128 * 1024;
+  s.sort_begin = s.fused ? std::min(8u, s.key_bits) : 0u;
+  // onesweep passes fed with digit counts from the recode (places = the
+  // 8-bit digits after the fused low byte); rocPRIM's radix_sort_keys
+  // otherwise (set_variant bit 10, or other tile shapes, or > 2 places)
+  s.places = (s.key_bits - s.sort_begin + 7) / 8;
+  s.own_sort = s.fused && !k.rocprim_hist && s.places <= 2 && entries < (size_t(1) << 32);
+  return s;
+}
+
+template <class Curve>
+typename MsmGpu<Curve>::AccFields MsmGpu<Curve>::acc_fields(int variant) {
+  AccFields f;
+  f.tree_reduce = (variant & 4096) != 0;  // bit 12: window sums by workgroup trees (A/B)
+  // BN254 G1 accumulates over the 29-bit-limb field with hand-chained products
+  // (field/f29_asm.h) and product-free conversions, the next base not
+  // prefetched (3 waves per SIMD): 2^26 accumulation 67.3 -> 61.0 ms, faster
+  // at every size from 2^16 (profiles/r03b/ab_acc29_conv.log).  Bit 18 forces
+  // the 32-bit FIPS field; bits 13 / 17 prefetch the next base in registers
+  // (2 waves) / through LDS by LDS-DMA (A/B); bit 14 is the default
+  const bool acc29_default = std::is_same_v<Curve, Bn254G1>;
+  f.acc29 = !(variant & 262144) && ((variant & (8192 | 16384 | 131072)) != 0 || acc29_default);
+  // BLS12-381 G1: the accumulation over 14 x 28-bit limbs (field/f28.h) by
+  // default; bit 20 restores the 12 x 32-bit FIPS field (A/B)
+  f.acc28 = std::is_same_v<Curve, Bls381G1> && !(variant & (1 << 20));
+  // G2: the lane pair over the 28-bit (BLS12-381, msm/pair28.h) / 29-bit
+  // (BN254, msm/pair29.h) field; bit 20 restores the FIPS pair, bit 15 the
+  // one-lane FIPS kernel
+  f.pair_limb = (std::is_same_v<Curve, Bls381G2> || std::is_same_v<Curve, Bn254G2>) && !(variant & (1 << 20));
+  // G2: a lane pair per point with inline products by default (BLS12-381 G2
+  // 2^24 accumulation 129 -> 113 ms, BN254 G2 2^22 16.3 -> 15.7 ms); bit 15
+  // restores the one-lane kernel, bit 16 the pair with out-of-line 12-limb products
+  f.pair_acc = !(variant & 32768);
+  return f;
+}
+
+// bucket sums and pieces in the 144-byte Raw format after the 29-bit
+// accumulation (not with the workgroup-tree window sums, an A/B path in R form)
+// (BLS12-381 G1: 224-byte Pol28::Raw after the 28-bit accumulation, read by
+// the 28-bit reductions -- not with the FIPS reductions of bit 22 or the
+// two-level window sums of bit 23; every join level raw, so the level buffer
+// takes the raw slot too)
+// (G2 lane pairs over the limb fields: 8 raw components per point -- 448 B
+// BLS12-381, 288 B BN254 -- not with the FIPS pair reductions (bit 22), the
+// two-level (bit 23) or two-pass (bit 24) window sums)
+template <class Curve>
+typename MsmGpu<Curve>::SlotBytes MsmGpu<Curve>::slot_bytes(const AccFields& f, int variant) {
+  SlotBytes s{sizeof(Point), sizeof(Point), false};
+  if constexpr (std::is_same_v<Curve, Bn254G1>) {
+    s.raw = f.acc29 && !f.tree_reduce;
+    if (s.raw) s.slot = sizeof(acc29::Raw);
+  }
+  if constexpr (std::is_same_v<Curve, Bls381G1>) {
+    s.raw = f.acc28 && !f.tree_reduce && !(variant & ((1 << 22) | (1 << 23)));
+    if (s.raw) s.slot = s.lvl_slot = sizeof(Pol28::Raw);
+  }
+  if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>) {
+    using LimbPol = std::conditional_t<std::is_same_v<Curve, Bls381G2>, PairPol28, PairPol29>;
+    s.raw = f.pair_acc && f.pair_limb && !f.tree_reduce && !(variant & ((1 << 22) | (1 << 23) | (1 << 24)));
+    if (s.raw) s.slot = s.lvl_slot = 8 * sizeof(typename LimbPol::F);
+  }
+  return s;
+}
+
 // Device bytes of the working buffers enqueue() grows for an n-point MSM
 // (keys/values and their sort double buffers, sort scratch, accumulation
-// pieces and chain tables, bucket and segment sums), plus 10 %.
+// pieces and chain tables, bucket and segment sums), plus 10 %.  The slot
+// sizes come from slot_bytes and the plan from run_plan, as enqueue's do.
 template <class Curve>
-size_t MsmGpu<Curve>::work_bytes(size_t n, unsigned c) const {
-  const MsmPlan p = MsmPlan::make(n, Fr::Config::kModulusBits, c, range_begin_, range_end_);
+size_t MsmGpu<Curve>::work_bytes(size_t n, unsigned c, size_t batch) const {
+  const MsmPlan p = run_plan(n, c);
   const size_t entries = n * p.active();
   const size_t T = (entries + p.K - 1) / p.K;
   size_t bytes = entries * 16 + entries / 2;                 // entries (x2) + onesweep scratch
-  // (pieces and bucket sums in the 144-byte Raw format of the BN254 G1 accumulation)
-  const size_t slot = std::is_same_v<Curve, Bn254G1> ? std::max<size_t>(sizeof(Point), 144) : sizeof(Point);
-  bytes += 2 * T * slot + (2 * T / kJoinFanLong + T + 2) * sizeof(Point);  // pieces + first join level
+  // rocPRIM's radix sort instead of the recode-fed onesweep passes (a recode
+  // scatter past 128 KiB of LDS: many narrow windows; set_variant bits 7, 10):
+  // its scratch holds another copy of the entries
+  const unsigned W = (unsigned)(p.active() * batch), G = batch > 1 ? W : std::max(1u, std::min(p.group, W));
+  if (!sort_shape(sort_knobs(variant_), p.c, p.active(), W, G, entries).own_sort) bytes += entries * 8;
+  const SlotBytes sb = slot_bytes(acc_fields(variant_), variant_);
+  const size_t slot = sb.slot;
+  bytes += 2 * T * slot + (2 * T / kJoinFanLong + T + 2) * sb.lvl_slot;     // pieces + first join level
   bytes += (T + 2) * 4 * 11;                                               // flags (x2), last bucket (x2), chain tables
   bytes += (T + 2) * 4 * 12;                                               // join-level offsets (<= 12 levels of <= T chains)
-  bytes += (size_t)p.active() * p.buckets * slot;                           // bucket sums
-  bytes += 2 * (size_t)p.active() * (p.buckets / p.seg) * sizeof(Point);
+  // (a batch of `batch` MSMs over n points in all keeps a block of windows per MSM)
+  bytes += batch * p.active() * p.buckets * slot;                           // bucket sums
+  // segment sums (x2), where the window sums are not one scan launch per window
+  if (!window_sums_by_scan(acc_fields(variant_), p.buckets))
+    bytes += 2 * batch * p.active() * (p.buckets / p.seg) * sizeof(Point);
   return bytes + bytes / 10;
 }
 

@@ -216,6 +216,17 @@ class VariableBaseMSMGpu:
         """Point chunks the last run was split into (device memory or host-upload pipeline)."""
         return lib().tachyon_mi355x_msm_gpu_last_divisions(self.curve_id, self._ctx)
 
+    def run_bytes(self, n: int, count: int = 0) -> int:
+        """The estimated device working set (bytes, margin included) of an
+        n-point run under this context's window bits and variant, or with
+        count > 0 of run_batch over count MSMs of n points -- what the run is
+        divided by (tachyon_mi355x_msm_gpu_run_bytes)."""
+        return lib().tachyon_mi355x_msm_gpu_run_bytes(self.curve_id, self._ctx, n, count)
+
+    def held_bytes(self) -> int:
+        """Bytes of the working buffers this context holds now (tachyon_mi355x_msm_gpu_held_bytes)."""
+        return lib().tachyon_mi355x_msm_gpu_held_bytes(self.curve_id, self._ctx)
+
     def last_timings(self) -> dict:
         out = (ctypes.c_float * 8)()
         lib().tachyon_mi355x_msm_gpu_last_timings(self.curve_id, self._ctx, out)

@@ -48,6 +48,16 @@ def test_library_loads_and_binds_signatures(libpath):
     assert b"gfx950" in L.tachyon_mi355x_version()
 
 
+def test_msm_memory_accessors_take_a_null_context(libpath):
+    """tachyon_mi355x_msm_gpu_run_bytes / _held_bytes: 0 for a null context on
+    every curve id, a bad one included (no GPU call, no abort)."""
+    from tachyon_amd._lib import lib
+    for curve in (0, 1, 2, 3, 9):
+        assert lib().tachyon_mi355x_msm_gpu_run_bytes(curve, None, 1 << 20, 0) == 0
+        assert lib().tachyon_mi355x_msm_gpu_run_bytes(curve, None, 1 << 10, 8) == 0
+        assert lib().tachyon_mi355x_msm_gpu_held_bytes(curve, None) == 0
+
+
 def test_code_object_targets_gfx950(libpath):
     # the fat binary carries one code object, for gfx950 only
     data = open(libpath, "rb").read()

@@ -315,3 +315,57 @@ def test_library_shard_plan_gloo(curve, n, world, groups):
         assert p.exitcode == 0
     for rank, g, total, want in got:
         assert g == groups and total == want, rank
+
+
+def _bad_plan_worker(rank, world, port, log_dir, q):
+    """tachyon_mi355x_msm_gpu_sharded_plan_affine with rank 1 holding a plan
+    made for a world of 3 (no GPU here: the contexts are null, so rank 0's
+    local part fails too, but only after its plan was accepted)."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    # the library reports the reason on stderr: keep this rank's in a file
+    err = os.open(os.path.join(log_dir, f"rank{rank}.err"), os.O_WRONLY | os.O_CREAT | os.O_TRUNC)
+    os.dup2(err, 2)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import ctypes
+        import time
+        from tachyon_amd import dist as D
+        from tachyon_amd import msm as M
+        from tachyon_amd._lib import lib
+        comm = D.LibComm.from_process_group()
+        n = 300
+        s = M.shard_plan("bn254_g1", n, world if rank == 0 else 3, rank)
+        out = ctypes.create_string_buffer(64)
+        t0 = time.time()
+        rc = lib().tachyon_mi355x_msm_gpu_sharded_plan_affine(0, None, comm.handle, ctypes.byref(s), None, None, out)
+        dt = time.time() - t0
+        after = comm.all_gather(bytes([rank]))  # the communicator still works
+        comm.close()
+        q.put((rank, rc, out.raw == bytes(64), dt, after))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libtachyon_mi355x.so not built")
+def test_sharded_plan_for_another_world_fails_on_every_rank(tmp_path):
+    """A shard plan is checked against the communicator inside the exchange:
+    the rank with a world-3 plan on a world-2 communicator enters the
+    all-gather with a failure flag, both ranks return 0 (out untouched) within
+    the timeout, and the communicator stays usable."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_bad_plan_worker, args=(r, 2, port, str(tmp_path), q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = sorted(q.get(timeout=240) for _ in range(2))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, rc, untouched, dt, after in got:
+        assert rc == 0 and untouched and after == bytes([0, 1]), rank
+        assert dt < 120, rank
+    errs = [open(tmp_path / f"rank{r}.err").read() for r in range(2)]
+    assert "on a communicator of 2" in errs[1]      # rank 1: its plan was refused
+    # rank 0's plan was accepted: it got as far as its (here null) context
+    assert "on a communicator of 2" not in errs[0] and "null MSM context" in errs[0]

@@ -168,9 +168,11 @@ def test_cpp_sharded_client_world1(tmp_path):
 
 def test_rccl_sharded_plan_entry_world1():
     """tachyon_mi355x_msm_gpu_sharded_plan_affine over the RCCL communicator at
-    world 1: the library's own plan (one point shard: the whole MSM), and a
-    hybrid shard of two window ranges (each range's partial is the window-range
-    MSM at the shard's window bits; the two partials add up to the MSM)."""
+    world 1: the library's own plan (one point shard: the whole MSM), and the
+    same shard naming every window at its own window bits.  (A hybrid plan of
+    two window ranges is a plan for two ranks: the entry refuses it at world 1,
+    test_sharded_plan_checked_against_the_communicator_world1; the two ranges
+    run on two ranks in test_host_staged_sharded_plan_world2.)"""
     from tachyon_amd import dist as D
     from tachyon_amd import msm as M
     from tachyon_amd._lib import MsmShard
@@ -187,15 +189,60 @@ def test_rccl_sharded_plan_entry_world1():
     assert m.run_sharded_plan(comm, s, db, ds) == want
     c = 13
     W = D._windows_for("bn254_g1", c)
-    parts = []
-    for w0, w1 in (D.window_range(W, 0, 2), D.window_range(W, 1, 2)):
-        got = m.run_sharded_plan(comm, MsmShard(0, n, 1, 2, c, w0, w1), db, ds)
-        m.set_window_bits(c)
-        assert got == m.run_window_range(db, ds, w0, w1, n), (w0, w1)
-        m.set_window_bits(0)
-        parts.append(got)
+    assert m.run_sharded_plan(comm, MsmShard(0, n, 1, 1, c, 0, W), db, ds) == want
+    # the window ranges such a plan names, run directly: the partials add up to the MSM
+    m.set_window_bits(c)
+    parts = [m.run_window_range(db, ds, w0, w1, n) for w0, w1 in (D.window_range(W, 0, 2), D.window_range(W, 1, 2))]
+    m.set_window_bits(0)
     assert M.affine_sum("bn254_g1", b"".join(parts)) == want
-    assert m.window_bits == 0 and m.run(db, ds) == want  # the entry restored the context's window bits
+    assert m.window_bits == 0 and m.run(db, ds) == want  # the context's window bits are the caller's again
+    m.close()
+    comm.close()
+
+
+def test_sharded_plan_checked_against_the_communicator_world1():
+    """tachyon_mi355x_msm_gpu_sharded_plan_affine refuses a plan that does not
+    match the call (returns 0, out untouched) instead of summing the wrong
+    partials: a plan made for world 2 on a world-1 communicator (point shards
+    and the hybrid), w_end above the window count of the plan's window bits,
+    w_begin > w_end, a null plan and an unknown curve id.  After each refusal
+    a good plan still gives the MSM."""
+    import ctypes
+    from tachyon_amd import dist as D
+    from tachyon_amd import msm as M
+    from tachyon_amd._lib import MsmShard, lib
+    comm = D.LibComm.rccl()
+    n = 6000
+    bases = O.gen_bases("bn254_g1", 8, n, 64).tobytes()
+    scalars = O.gen_scalars("bn254_fr", 8, n).tobytes()
+    want = O.msm("bn254_g1", bases, scalars)[0]
+    db = torch.frombuffer(bytearray(bases), dtype=torch.uint8).cuda()
+    ds = torch.frombuffer(bytearray(scalars), dtype=torch.uint8).cuda()
+    m = M.VariableBaseMSMGpu("bn254_g1")
+    good = M.shard_plan("bn254_g1", n, 1, 0)
+    c = 13
+    W = D._windows_for("bn254_g1", c)
+
+    def entry(curve_id, plan):
+        out = ctypes.create_string_buffer(64)
+        rc = lib().tachyon_mi355x_msm_gpu_sharded_plan_affine(curve_id, m._ctx, comm.handle, plan, db.data_ptr(),
+                                                             ds.data_ptr(), out)
+        return rc, out.raw
+
+    two = M.shard_plan("bn254_g1", n, 2, 0)  # rank 0's point shard of a world of 2
+    assert (two.point_groups, two.window_groups) == (2, 1)
+    bad = [(0, ctypes.byref(two)),
+           (0, ctypes.byref(MsmShard(0, n, 1, 2, c, 0, W // 2))),     # hybrid for world 2
+           (0, ctypes.byref(MsmShard(0, n, 1, 1, c, 0, W + 1))),      # one window too many
+           (0, ctypes.byref(MsmShard(0, n, 1, 1, 0, 0, M.plan("bn254_g1", n)[1] + 1))),  # ... at the default bits
+           (0, ctypes.byref(MsmShard(0, n, 1, 1, c, 5, 4))),          # w_begin > w_end
+           (0, None),                                                 # null plan
+           (7, ctypes.byref(good))]                                   # unknown curve id
+    for curve_id, plan in bad:
+        assert entry(curve_id, plan) == (0, bytes(64))
+        assert m.run_sharded_plan(comm, good, db, ds) == want
+    # the largest range a plan may name is still accepted
+    assert entry(0, ctypes.byref(MsmShard(0, n, 1, 1, c, 0, W))) == (1, want)
     m.close()
     comm.close()
 
