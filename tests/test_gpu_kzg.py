@@ -5,6 +5,7 @@ Commit(poly) == CommitLagrange(FFT(poly)), batch commitments, Downsize, and the
 tau-in-the-domain corner of EvaluateAllLagrangeCoefficients."""
 import pytest
 
+import kzg_ref
 from oracle import oracle as O
 from oracle import pyref
 
@@ -13,22 +14,8 @@ pytestmark = pytest.mark.gpu
 
 def oracle_srs(curve, n, tau):
     """[tau^i] G and [L_i(tau)] G (affine bytes), L_i over the size-n radix-2 domain."""
-    C = pyref.Curve(curve)
-    Fr = C.Fr
-    r = Fr.p
-    w = Fr.root_of_unity(n)
-    g = C.to_bytes(C.G)
-    mul = lambda k: O.ec_op(curve, "mul", g, k.to_bytes(32, "little"))  # plain-integer scalar
-    powers = b"".join(mul(pow(tau, i, r)) for i in range(n))
-    z = (pow(tau, n, r) - 1) % r
-    lag = []
-    for i in range(n):
-        wi = pow(w, i, r)
-        if z == 0:
-            lag.append(1 if wi == tau else 0)
-        else:
-            lag.append(z * pow(n, -1, r) * wi * pow((tau - wi) % r, -1, r) % r)
-    return powers, b"".join(mul(k) for k in lag)
+    s, l = kzg_ref.srs_scalars(kzg_ref.SCALAR_FIELD[curve], n, tau)
+    return kzg_ref.srs_points(curve, s), kzg_ref.srs_points(curve, l)
 
 
 @pytest.mark.parametrize("curve,logn", [("bn254_g1", 3), ("bn254_g1", 6), ("bls12_381_g1", 4)])
