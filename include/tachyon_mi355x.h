@@ -1174,6 +1174,76 @@ TACHYON_C_EXPORT int tachyon_mi355x_kzg_commit_batch(tachyon_mi355x_kzg* kzg, in
                                                      const void* const* scalars, const size_t* lens, size_t count,
                                                      void* out_affine);
 
+/* KZG openings: the family's CreateOpeningProof (kzg/gwc.h:83-122,
+ * kzg/shplonk.h:84-226, grouping in commitments/polynomial_openings.h) on
+ * polynomials that stay in device memory.  Polynomials are coefficient
+ * vectors of any length >= 0, lowest degree first, host or device, ragged
+ * within a call; an opening is (poly_idx[i], points[i], values[i]), points
+ * and values host arrays of 32-byte Montgomery elements.  A polynomial's
+ * identity is its index.
+ *
+ * The transcript is the caller's (a TranscriptWriter behind the callbacks):
+ *   squeeze_challenge(ctx, out_fr)  writes the challenge, Montgomery form;
+ *   write_to_proof(ctx, affine)     returns 0 when the write failed.
+ * They are called in the reference's order -- scheme 0 (GWC): v, then every
+ * W_g in group order; scheme 1 (SHPlonk): y, v, write H, u, write Q.
+ *
+ * create_opening_proof also copies the commitments it wrote to
+ * out_affine[0 .. *out_count).  Returns 0 with no device work and no callback
+ * made when: an index is out of range, a polynomial is longer than N, an
+ * array is null with a nonzero count, two SHPlonk openings of one
+ * (polynomial, point) claim different values, cap is below the number of
+ * commitments (groups for GWC, 2 for SHPlonk), SHPlonk is given no opening
+ * at all (GWC then writes nothing and returns 1).  Returns 0 after the fact when
+ * a write_to_proof returned 0 or SHPlonk's Z_{T \ 0}(u) is zero (the reference
+ * CHECKs); it never aborts for these.
+ *
+ * evaluate_batch: out[i] = polys[poly_idx[i]](points[i]), the empty
+ * polynomial evaluating to 0 (one launch per level for the whole batch).
+ * last_open_timings: milliseconds (stream events) of the last call's phases:
+ * evaluate, combine, divide, commit. */
+typedef struct {
+  void (*squeeze_challenge)(void* ctx, void* out_fr);
+  int (*write_to_proof)(void* ctx, const void* affine_commitment);
+  void* ctx;
+} tachyon_mi355x_kzg_transcript;
+TACHYON_C_EXPORT int tachyon_mi355x_kzg_evaluate_batch(tachyon_mi355x_kzg* kzg, const void* const* polys,
+                                                       const size_t* lens, size_t num_polys, const size_t* poly_idx,
+                                                       const void* points, size_t count, void* out);
+TACHYON_C_EXPORT int tachyon_mi355x_kzg_create_opening_proof(tachyon_mi355x_kzg* kzg, int scheme,
+                                                             const void* const* polys, const size_t* lens,
+                                                             size_t num_polys, const size_t* poly_idx,
+                                                             const void* points, const void* values,
+                                                             size_t num_openings,
+                                                             const tachyon_mi355x_kzg_transcript* transcript,
+                                                             void* out_affine, size_t cap, size_t* out_count);
+TACHYON_C_EXPORT void tachyon_mi355x_kzg_last_open_timings(const tachyon_mi355x_kzg* kzg, float* out_ms);
+/* The polynomial kernels on their own (curve: 0 bn254, 2 bls12-381 scalar
+ * field; no SRS).  Inputs and outputs host or device.
+ *   linear_combination: out[k] = sum_i coeffs[i] polys[i][k] - d [k == 0] for
+ *     k < out_len, which must equal the longest input; d may be null (0).
+ *   divide_by_roots: poly / prod_j (X - roots[j]), remainders dropped: the
+ *     quotient's max(len, nroots) - nroots coefficients to out_quotient;
+ *     out_remainders (or null) receives, per root, the remainder of its step
+ *     (the value at roots[j] of the quotient by the roots before it).
+ * Return 0 on a null array with a nonzero count or a wrong out_len. */
+TACHYON_C_EXPORT int tachyon_mi355x_kzg_poly_linear_combination(int curve, const void* const* polys,
+                                                                const size_t* lens, const void* coeffs, size_t count,
+                                                                const void* d, void* out, size_t out_len);
+TACHYON_C_EXPORT int tachyon_mi355x_kzg_poly_divide_by_roots(int curve, const void* poly, size_t len,
+                                                             const void* roots, size_t nroots, void* out_quotient,
+                                                             void* out_remainders);
+/* The grouping and validation alone: host code, no GPU needed.  out receives
+ * 64-bit words: the group count, then per group the point count, the points
+ * (4 words each, as given), the polynomial count and the polynomial indices;
+ * *out_words their number.  A group's points are in the field's order.
+ * Returns 0 on the refusals above (n: the SRS size the lengths are checked
+ * against) or when cap words do not suffice (*out_words is still set). */
+TACHYON_C_EXPORT int tachyon_mi355x_kzg_opening_plan(int curve, int scheme, const size_t* lens, size_t num_polys,
+                                                     size_t n, const size_t* poly_idx, const void* points,
+                                                     const void* values, size_t num_openings, uint64_t* out,
+                                                     size_t cap, size_t* out_words);
+
 /* delete a Jacobian returned by an *_msm / *_msm_gpu entry point (for callers
  * that cannot use C++ delete, e.g. ctypes). */
 TACHYON_C_EXPORT void tachyon_mi355x_jacobian_destroy(int curve, void* jacobian);

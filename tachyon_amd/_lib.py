@@ -44,6 +44,16 @@ class FriRound(ctypes.Structure):
                 ("num_points", ctypes.POINTER(ctypes.c_size_t)), ("opened_values_out", ctypes.POINTER(ctypes.c_void_p))]
 
 
+# tachyon_mi355x_kzg_transcript's callbacks: (ctx, out_fr) and (ctx, affine) -> 0 when the write failed
+KZG_SQUEEZE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)
+KZG_WRITE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p)
+
+
+class KzgTranscript(ctypes.Structure):
+    """tachyon_mi355x_kzg_transcript: the caller's transcript behind two callbacks and a context."""
+    _fields_ = [("squeeze_challenge", KZG_SQUEEZE_FN), ("write_to_proof", KZG_WRITE_FN), ("ctx", ctypes.c_void_p)]
+
+
 SIGNATURES = [
     # reference C-ABI: MSM
     ("tachyon_bn254_g1_init", None, []),
@@ -191,6 +201,21 @@ SIGNATURES = [
     ("tachyon_mi355x_kzg_commit", i32, [vp, i32, vp, sz, vp]),
     ("tachyon_mi355x_kzg_commit_batch", i32, [vp, i32, ctypes.POINTER(ctypes.c_void_p),
                                               ctypes.POINTER(ctypes.c_size_t), sz, vp]),
+    # KZG openings: evaluate, GWC / SHPlonk proofs, the polynomial primitives, the grouping
+    ("tachyon_mi355x_kzg_evaluate_batch", i32, [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
+                                                sz, ctypes.POINTER(ctypes.c_size_t), vp, sz, vp]),
+    ("tachyon_mi355x_kzg_create_opening_proof", i32, [vp, i32, ctypes.POINTER(ctypes.c_void_p),
+                                                      ctypes.POINTER(ctypes.c_size_t), sz,
+                                                      ctypes.POINTER(ctypes.c_size_t), vp, vp, sz,
+                                                      ctypes.POINTER(KzgTranscript), vp, sz,
+                                                      ctypes.POINTER(ctypes.c_size_t)]),
+    ("tachyon_mi355x_kzg_last_open_timings", None, [vp, fp]),
+    ("tachyon_mi355x_kzg_poly_linear_combination", i32, [i32, ctypes.POINTER(ctypes.c_void_p),
+                                                         ctypes.POINTER(ctypes.c_size_t), vp, sz, vp, vp, sz]),
+    ("tachyon_mi355x_kzg_poly_divide_by_roots", i32, [i32, vp, sz, vp, sz, vp, vp]),
+    ("tachyon_mi355x_kzg_opening_plan", i32, [i32, i32, ctypes.POINTER(ctypes.c_size_t), sz, sz,
+                                              ctypes.POINTER(ctypes.c_size_t), vp, vp, sz,
+                                              ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_size_t)]),
     # field-generic NTT domains
     ("tachyon_mi355x_ntt_domain_create", vp, [i32, sz]),
     ("tachyon_mi355x_ntt_domain_destroy", None, [vp]),

@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "../capi/kzg_open_validate.h"
 #include "../field/curve_constants.h"
 #include "../ntt/ntt.h"
 
@@ -215,6 +216,281 @@ bool Kzg<Curve>::commit_batch(const Fr* const* scalars, const size_t* lens, size
 template <class Curve>
 void Kzg<Curve>::copy_srs(bool lagrange, Aff* host_out) const {
   TA_HIP(hipMemcpy(host_out, d_srs(lagrange), n_ * sizeof(Aff), hipMemcpyDeviceToHost));
+}
+
+namespace {
+
+// Stream-event spans of the phases of one call (0 evaluate, 1 combine,
+// 2 divide, 3 commit), summed per phase when the call ends
+class PhaseTimer {
+ public:
+  explicit PhaseTimer(hipStream_t stream) : stream_(stream) {}
+  ~PhaseTimer() {
+    for (auto& s : spans_) {
+      (void)hipEventDestroy(s.start);
+      (void)hipEventDestroy(s.stop);
+    }
+  }
+  void begin(int phase) {
+    Span s{phase, nullptr, nullptr};
+    TA_HIP(hipEventCreate(&s.start));
+    TA_HIP(hipEventCreate(&s.stop));
+    TA_HIP(hipEventRecord(s.start, stream_));
+    spans_.push_back(s);
+  }
+  void end() { TA_HIP(hipEventRecord(spans_.back().stop, stream_)); }
+  // after the stream has been synchronised
+  void finish(float* ms) {
+    for (int i = 0; i < 4; ++i) ms[i] = 0;
+    for (auto& s : spans_) {
+      float t = 0;
+      TA_HIP(hipEventSynchronize(s.stop));
+      TA_HIP(hipEventElapsedTime(&t, s.start, s.stop));
+      ms[s.phase] += t;
+    }
+  }
+
+ private:
+  struct Span {
+    int phase;
+    hipEvent_t start, stop;
+  };
+  hipStream_t stream_;
+  std::vector<Span> spans_;
+};
+
+// Coefficients of the interpolant of (x_k, y_k), k < n, the x_k distinct
+// (math::LagrangeInterpolate): sum_k y_k prod_{i != k} (X - x_i) / (x_k - x_i)
+template <class Fr>
+std::vector<Fr> lagrange_interpolate(const std::vector<Fr>& x, const std::vector<Fr>& y) {
+  const size_t n = x.size();
+  std::vector<Fr> r(n, Fr::zero());
+  for (size_t k = 0; k < n; ++k) {
+    std::vector<Fr> num{Fr::one()};
+    Fr den = Fr::one();
+    for (size_t i = 0; i < n; ++i) {
+      if (i == k) continue;
+      num.push_back(Fr::zero());  // num *= (X - x_i)
+      for (size_t j = num.size() - 1; j > 0; --j) num[j] = num[j - 1] - x[i] * num[j];
+      num[0] = -(x[i] * num[0]);
+      den = den * (x[k] - x[i]);
+    }
+    const Fr s = y[k] * den.inverse();
+    for (size_t j = 0; j < n; ++j) r[j] = r[j] + s * num[j];
+  }
+  return r;
+}
+
+template <class Fr>
+Fr horner(const std::vector<Fr>& p, const Fr& z) {
+  Fr acc = Fr::zero();
+  for (size_t j = p.size(); j-- > 0;) acc = p[j] + z * acc;
+  return acc;
+}
+
+}  // namespace
+
+template <class Curve>
+bool Kzg<Curve>::evaluate_batch(const Fr* const* polys, const size_t* lens, size_t count, const size_t* idx,
+                                const Fr* points, size_t m, Fr* out) {
+  if (m != 0 && (!idx || !points || !out)) return false;
+  if (count != 0 && (!polys || !lens)) return false;
+  for (size_t i = 0; i < count; ++i)
+    if (lens[i] != 0 && !polys[i]) return false;
+  for (size_t i = 0; i < m; ++i)
+    if (idx[i] >= count) return false;
+  if (!poly_) poly_ = std::make_unique<PolyOps<Fr>>(stream_);
+  PhaseTimer timer(stream_);
+  std::vector<const Fr*> dev;
+  poly_->stage(polys, lens, count, &dev);
+  std::vector<typename PolyOps<Fr>::Pair> pairs(m);
+  for (size_t i = 0; i < m; ++i) pairs[i] = {dev[idx[i]], lens[idx[i]], points[i]};
+  timer.begin(0);
+  poly_->evaluate(pairs.data(), m, out);
+  timer.end();
+  poly_->synchronize();
+  timer.finish(open_ms_);
+  return true;
+}
+
+template <class Curve>
+bool Kzg<Curve>::create_opening_proof(int scheme, const Fr* const* polys, const size_t* lens, size_t count,
+                                      const size_t* idx, const Fr* points, const Fr* values, size_t m,
+                                      const Transcript& transcript, Aff* out, size_t cap, size_t* out_count) {
+  using Term = typename PolyOps<Fr>::Term;
+  if (!transcript.squeeze_challenge || !transcript.write_to_proof || !out_count || (cap != 0 && !out)) return false;
+  kzg_open::Openings o;
+  o.poly = idx;
+  o.points = reinterpret_cast<const unsigned char*>(points);
+  o.values = reinterpret_cast<const unsigned char*>(values);
+  o.elem_bytes = sizeof(Fr);
+  o.count = m;
+  if (count != 0 && !polys) return false;
+  kzg_open::Plan plan;
+  if (!kzg_open::make_plan(scheme, o, lens, count, n_, element_less<Fr>, &plan)) return false;
+  for (size_t i = 0; i < count; ++i)
+    if (lens[i] != 0 && !polys[i]) return false;
+  const size_t num_groups = plan.groups.size();
+  if (cap < (scheme == kzg_open::kGwc ? num_groups : 2)) return false;
+  // SHPlonk normalises by the first group's Z_{T\0}(u): nothing to open, no proof
+  if (scheme == kzg_open::kShplonk && num_groups == 0) return false;
+
+  if (!poly_) poly_ = std::make_unique<PolyOps<Fr>>(stream_);
+  PhaseTimer timer(stream_);
+  std::vector<const Fr*> dev;
+  poly_->stage(polys, lens, count, &dev);
+  auto squeeze = [&] {
+    Fr c;
+    transcript.squeeze_challenge(transcript.ctx, &c);
+    return c;
+  };
+  auto done = [&](bool ok) {
+    poly_->synchronize();
+    timer.finish(open_ms_);
+    return ok;
+  };
+  auto commit_and_write = [&](const std::vector<const Fr*>& ptrs, const std::vector<size_t>& qlens) {
+    std::vector<Aff> affs(ptrs.size());
+    timer.begin(3);
+    const bool ok = commit_batch(ptrs.data(), qlens.data(), ptrs.size(), false, affs.data());
+    timer.end();
+    if (!ok) return false;
+    for (const Aff& a : affs) {
+      out[(*out_count)++] = a;
+      if (!transcript.write_to_proof(transcript.ctx, &a)) return false;
+    }
+    return true;
+  };
+  *out_count = 0;
+  // the longest polynomial of each group, and room for every group's quotient
+  std::vector<size_t> glen(num_groups, 0), qlen(num_groups), qoff(num_groups);
+  size_t quot_total = 0, num_len = 0, low_total = 0;
+  for (size_t g = 0; g < num_groups; ++g) {
+    const kzg_open::Group& grp = plan.groups[g];
+    for (size_t p : grp.polys) glen[g] = std::max(glen[g], lens[p]);
+    if (scheme == kzg_open::kShplonk) glen[g] = std::max(glen[g], grp.points.size());  // the interpolants
+    qlen[g] = glen[g] - std::min(glen[g], grp.points.size());
+    qoff[g] = quot_total;
+    quot_total += qlen[g];
+    low_total += grp.points.size();
+    num_len = std::max(num_len, glen[g]);
+  }
+  Fr* quot = static_cast<Fr*>(open_quot_.ensure(std::max<size_t>(1, quot_total) * sizeof(Fr)));
+  Fr* num = static_cast<Fr*>(open_num_.ensure(std::max<size_t>(1, num_len) * sizeof(Fr)));
+
+  if (scheme == kzg_open::kGwc) {
+    // W_g = (sum_j v^j P_j - sum_j v^j P_j(x_g)) / (X - x_g), j over the group's openings
+    const Fr v = squeeze();
+    std::vector<const Fr*> ptrs(num_groups);
+    for (size_t g = 0; g < num_groups; ++g) {
+      const kzg_open::Group& grp = plan.groups[g];
+      std::vector<Term> terms;
+      Fr c = Fr::one(), d = Fr::zero();
+      for (size_t j = 0; j < grp.polys.size(); ++j, c = c * v) {
+        terms.push_back({dev[grp.polys[j]], lens[grp.polys[j]], c});
+        d = d + c * values[grp.values[j]];
+      }
+      timer.begin(1);
+      poly_->linear_combination(terms.data(), terms.size(), d, num, glen[g]);
+      timer.end();
+      timer.begin(2);
+      poly_->divide_by_roots(num, glen[g], &points[grp.points[0]], 1, quot + qoff[g], nullptr);
+      timer.end();
+      ptrs[g] = quot + qoff[g];
+    }
+    return done(commit_and_write(ptrs, qlen));
+  }
+
+  // SHPlonk.  R_j: the interpolant of polynomial j's claimed values on its
+  // group's points; Rc_g = sum_j y^j R_j enters the numerator as one more
+  // (low-degree) input with coefficient -1.
+  const Fr y = squeeze();
+  std::vector<std::vector<Fr>> group_points(num_groups);
+  std::vector<std::vector<std::vector<Fr>>> interp(num_groups);
+  std::vector<Fr> low(low_total);
+  Fr* d_low = static_cast<Fr*>(open_low_.ensure(std::max<size_t>(1, low_total) * sizeof(Fr)));
+  size_t low_off = 0;
+  std::vector<size_t> low_offs(num_groups);
+  for (size_t g = 0; g < num_groups; ++g) {
+    const kzg_open::Group& grp = plan.groups[g];
+    const size_t k = grp.points.size();
+    for (size_t pt : grp.points) group_points[g].push_back(points[pt]);
+    low_offs[g] = low_off;
+    Fr c = Fr::one();
+    for (size_t j = 0; j < grp.polys.size(); ++j, c = c * y) {
+      std::vector<Fr> vals(k);
+      for (size_t i = 0; i < k; ++i) vals[i] = values[grp.values[j * k + i]];
+      interp[g].push_back(lagrange_interpolate(group_points[g], vals));
+      for (size_t i = 0; i < k; ++i) low[low_off + i] = (j ? low[low_off + i] : Fr::zero()) + c * interp[g][j][i];
+    }
+    low_off += k;
+  }
+  if (low_total) TA_HIP(hipMemcpyAsync(d_low, low.data(), low_total * sizeof(Fr), hipMemcpyHostToDevice, stream_));
+  // H_g = (sum_j y^j P_j - Rc_g) / Z_g
+  for (size_t g = 0; g < num_groups; ++g) {
+    const kzg_open::Group& grp = plan.groups[g];
+    std::vector<Term> terms;
+    Fr c = Fr::one();
+    for (size_t j = 0; j < grp.polys.size(); ++j, c = c * y) terms.push_back({dev[grp.polys[j]], lens[grp.polys[j]], c});
+    terms.push_back({d_low + low_offs[g], grp.points.size(), -Fr::one()});
+    timer.begin(1);
+    poly_->linear_combination(terms.data(), terms.size(), Fr::zero(), num, glen[g]);
+    timer.end();
+    timer.begin(2);
+    poly_->divide_by_roots(num, glen[g], group_points[g].data(), grp.points.size(), quot + qoff[g], nullptr);
+    timer.end();
+  }
+  // H = sum_g v^g H_g
+  const Fr v = squeeze();
+  size_t h_len = 0;
+  for (size_t g = 0; g < num_groups; ++g) h_len = std::max(h_len, qlen[g]);
+  Fr* h = static_cast<Fr*>(open_h_.ensure(std::max<size_t>(1, 2 * num_len) * sizeof(Fr)));
+  {
+    std::vector<Term> terms;
+    Fr c = Fr::one();
+    for (size_t g = 0; g < num_groups; ++g, c = c * v) terms.push_back({quot + qoff[g], qlen[g], c});
+    timer.begin(1);
+    poly_->linear_combination(terms.data(), terms.size(), Fr::zero(), h, h_len);
+    timer.end();
+  }
+  if (!commit_and_write({h}, {h_len})) return done(false);
+  const Fr u = squeeze();
+  // Z_{T \ g}(u) for every group, Z_T(u); everything is scaled by
+  // 1 / Z_{T \ 0}(u) up front, so that Q = L / (X - u) needs no pass of its own
+  std::vector<Fr> z_diff(num_groups, Fr::one());
+  Fr z_t = Fr::one();
+  for (size_t s : plan.super_points) {
+    const Fr f = u - points[s];
+    z_t = z_t * f;
+    for (size_t g = 0; g < num_groups; ++g)
+      if (std::find(plan.groups[g].points.begin(), plan.groups[g].points.end(), s) == plan.groups[g].points.end())
+        z_diff[g] = z_diff[g] * f;
+  }
+  if (z_diff[0].is_zero()) return done(false);
+  const Fr inv0 = z_diff[0].inverse();
+  // L = sum_g v^g Z_{T\g}(u) sum_j y^j (P_j - R_j(u)) - Z_T(u) H
+  std::vector<Term> terms;
+  Fr d = Fr::zero(), vg = Fr::one();
+  size_t l_len = h_len;
+  for (size_t g = 0; g < num_groups; ++g, vg = vg * v) {
+    const kzg_open::Group& grp = plan.groups[g];
+    const Fr scale = vg * z_diff[g] * inv0;
+    Fr c = scale;
+    for (size_t j = 0; j < grp.polys.size(); ++j, c = c * y) {
+      terms.push_back({dev[grp.polys[j]], lens[grp.polys[j]], c});
+      d = d + c * horner(interp[g][j], u);
+      l_len = std::max(l_len, lens[grp.polys[j]]);
+    }
+  }
+  terms.push_back({h, h_len, -(z_t * inv0)});
+  Fr* q = h + num_len;  // the second half of the buffer
+  timer.begin(1);
+  poly_->linear_combination(terms.data(), terms.size(), d, num, l_len);
+  timer.end();
+  timer.begin(2);
+  poly_->divide_by_roots(num, l_len, &u, 1, q, nullptr);
+  timer.end();
+  return done(commit_and_write({q}, {l_len ? l_len - 1 : 0}));
 }
 
 template class Kzg<Bn254G1>;
