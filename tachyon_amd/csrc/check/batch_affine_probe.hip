@@ -8,7 +8,7 @@
 //
 // Rows (one JSON line each, G additions per lane per round):
 //   madd_reg    the accumulation's madd-2008-s with the base in registers
-//               (madd_ceiling29_kernel of msm_impl.h, 3 waves per SIMD)
+//               (madd_ceiling29_kernel of msm/msm_ceiling.h, 3 waves per SIMD)
 //   madd_tab    the same with both coordinates read from a 64-point LDS table
 //               per addition (the batch rows read their points the same way)
 //   batch G     Montgomery's trick over G independent affine additions per

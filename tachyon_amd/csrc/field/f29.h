@@ -14,7 +14,7 @@
 // R' = 2^261 = 2^(29 * 9)), value = sum_i l_i 2^(29 i).  "N-form" (every
 // product's output): limbs 0..7 < 2^29, limb 8 the rest.  A product's inputs
 // may have wider limbs as long as every column stays below 2^64 (the bounds
-// are derived at each use in msm_impl.h, seg_acc29 / madd29).
+// are derived at each use in msm/msm_acc.h, seg_acc29 / madd29).
 //
 // Conversions to the 8 x 32-bit R = 2^256 form of the rest of the library:
 //   in : x' = x~ << 5 repacked (x~ the R-form value: x~ 2^5 = x 2^261), then

@@ -276,20 +276,52 @@ class MsmGpu {
   std::vector<Point> run_batch_impl(const void* bases, const void* scalars, size_t len, size_t count, bool distinct,
                                     unsigned fold = 1);
   void fold_bases_c(const void* bases, size_t n, unsigned fold, void* out, unsigned c);
+  // enqueue() is a sequence of stages over one Shape (what the run covers,
+  // const once made) and one Buffers (the device pointers cut for it); the
+  // structs and the stages are defined in msm_impl.h.  Keep the stages declared
+  // in the order they run: the kernel templates are emitted in the order the
+  // members first name them, and the accumulation kernels' place in the code
+  // object measured 3 % of the 2^16 accumulation (MSM section).
+  struct Shape;
+  struct Buffers;
+  struct ReduceKernels;  // the chain join's and the window sums' kernels of a run
+  struct AccLaunch;      // one group's accumulation kernel
   void enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, const MsmPlan& plan, Point* d_windows);
+  Shape make_shape(size_t n, const MsmPlan& plan) const;
+  Buffers carve(const Shape& s);
+  uint32_t* recode(const Shape& s, const Buffers& b, const Fr* d_scalars);
+  void sort_group(const Shape& s, const Buffers& b, unsigned g, size_t e0, size_t ecount, uint32_t* digit_off);
+  void upload_pending_bases(const Aff* d_bases, size_t n);
+  void early_chain_tables(const Shape& s, const Buffers& b, size_t e0, size_t ecount);
+  AccLaunch acc_launch(bool raw, int ent_mode) const;
+  void accumulate(const Shape& s, const Buffers& b, const Aff* d_bases, unsigned g, size_t e0, size_t ecount,
+                  size_t tbase);
+  ReduceKernels reduce_kernels(bool raw) const;
+  void check_early_flags(const Shape& s, const Buffers& b);
+  void join_offsets(const Shape& s, const Buffers& b, uint32_t nchains, unsigned K2, unsigned levels, uint32_t* ltab,
+                    size_t stride);
+  void join(const Shape& s, const Buffers& b, const ReduceKernels& rk);
+  void window_sums_two_level(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows);
+  void window_sums_by_trees(const Shape& s, const Buffers& b, Point* d_windows);
+  void window_sums(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows);
+  void window_sums_by_segments(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows);
   Point run_host_pipelined(const void* bases, const void* scalars, size_t n, size_t chunks);
   size_t work_bytes(size_t n, unsigned c, size_t batch = 1) const;
   // The plan of an n-point run under this context's variant bits (run_windows
   // and work_bytes: one rule for both).
   MsmPlan run_plan(size_t n, unsigned c) const;
-  // The field code the variant bits select (run_windows sets the members of
-  // the same names from it; work_bytes reads it before any run has).
+  // The field code the variant bits select (run_windows decodes it into acc_;
+  // work_bytes reads it before any run has): window sums by workgroup trees
+  // (bit 12); BN254 G1 over 29-bit limbs (default; bit 18: FIPS 32-bit);
+  // BLS12-381 G1 over 28-bit limbs (default; bit 20: FIPS); G2 with a lane pair
+  // per point (bit 15: one lane) over 28-bit (BLS12-381) / 29-bit (BN254)
+  // limbs (default; bit 20: the FIPS pair).
   struct AccFields {
     bool tree_reduce, acc29, acc28, pair_acc, pair_limb;
   };
   static AccFields acc_fields(int variant);
   // Bytes of one bucket sum / piece (`slot`) and of one join-level entry
-  // (`lvl_slot`), and whether they are raw limbs -- the one rule enqueue
+  // (`lvl_slot`), and whether they are raw limbs -- the one rule carve
   // allocates by and work_bytes estimates by.
   struct SlotBytes {
     size_t slot, lvl_slot;
@@ -298,7 +330,10 @@ class MsmGpu {
   static SlotBytes slot_bytes(const AccFields& f, int variant);
   static bool window_sums_by_scan(const AccFields& f, unsigned buckets);  // no segment sums then
   // The sort of a run's entries (enqueue) and what its scratch takes
-  // (work_bytes): the recode knobs of the variant bits, then the shape.
+  // (work_bytes): the recode knobs of the variant bits (the recode fused with
+  // the low-byte radix pass, bit 7 off; rocPRIM's digit histogram pass instead
+  // of the recode's counts, bit 10; 8-byte entries in the scatter's LDS
+  // staging, bit 11; scalars per thread of the fused recode), then the shape.
   struct SortKnobs {
     bool fuse_recode, rocprim_hist, wide_stage;
     uint32_t spt;
@@ -313,9 +348,7 @@ class MsmGpu {
   static SortShape sort_shape(const SortKnobs& k, unsigned c, unsigned Ws, unsigned W, unsigned G, size_t entries);
   size_t memory_divisions(size_t n, size_t resident_bytes) const;
   void ensure_group_events(unsigned groups);
-  void build_chains(const uint32_t* flags, const uint32_t* last, size_t T, unsigned K2, uint32_t* is_start,
-                    uint32_t* cid, uint32_t* cbeg, uint32_t* cend, uint32_t* cbucket, uint32_t* lcnt, uint32_t* dscal,
-                    hipStream_t s);
+  void build_chains(const Shape& s, const Buffers& b);
   hipError_t sort_entries(void* tmp, size_t& bytes, const uint64_t* in, uint64_t* out, size_t count,
                           unsigned begin_bit, unsigned end_bit, hipStream_t s);
 
@@ -327,32 +360,33 @@ class MsmGpu {
   MsmTimings timings_;
   DeviceBuffer bases_, scalars_, ents_, ents2_, sort_tmp_, scan_tmp_, check_;
   DeviceBuffer start_, end_, cnt_, off_a_, off_b_, part_a_, part_b_, seg_a_, seg_b_, windows_, buckets_;
-  hipEvent_t ev_[8] = {};  // 0-5 phase marks, 7 chain count read back (early chain tables)
+  // the phase marks of a profiled run, and the chain count read back (early chain tables)
+  enum Mark {
+    kMarkStart,
+    kMarkUploaded,
+    kMarkRecoded,
+    kMarkSorted,
+    kMarkAccumulated,
+    kMarkEnd,
+    kMarkChainsRead,
+    kMarks
+  };
+  hipEvent_t ev_[kMarks] = {};
   hipStream_t sort_stream_ = nullptr;  // group sorts run here, overlapping the accumulation on stream_
   std::vector<hipEvent_t> gev_sorted_, gev_acc0_, gev_acc1_;
   unsigned acc_launches_ = 0;
   unsigned sort_cfg_ = 0;  // onesweep tile shape (set_variant bits 4-5)
-  bool rocprim_hist_ = false;  // rocPRIM's digit histogram pass instead of the recode's counts (bit 10)
-  bool wide_stage_ = false;    // 8-byte entries in the recode scatter's LDS staging (bit 11)
-  bool tree_reduce_ = false;   // window sums by workgroup trees (bit 12)
-  bool acc29_ = false;         // BN254 G1 accumulation over 29-bit limbs (default; bit 18: FIPS 32-bit)
-  int acc29_mode_ = 0;         // ... next base: 0 not prefetched, 1 in registers (bit 13), 2 via LDS-DMA (bit 17)
-  bool pair_acc_ = false;      // G2 accumulation with a lane pair per point (bit 15)
-  bool acc28_ = false;         // BLS12-381 G1 accumulation over 28-bit limbs (default; bit 20: FIPS 32-bit)
-  bool pair_limb_ = false;     // G2 lane pair over 28-bit (BLS12-381) / 29-bit (BN254) limbs (default; bit 20: FIPS pair)
-  bool pair_inline_ = false;   // ... its 12-limb products inline (bit 16)
-  uint32_t idx_mask_ = 0x7FFFFFFFu;  // base-index mask of the accumulation gathers (strips the sign bit)
-  bool fuse_recode_ = true;          // recode fused with the low-byte radix pass
-  uint32_t recode_spt_ = 2;          // scalars per thread of the fused recode
+  SortKnobs sort_ = {};    // the variant bits of the current run, decoded (run_windows)
+  AccFields acc_ = {};
   bool scatter_lds_set_[2] = {false, false};  // 128 KiB dynamic LDS allowed: wide / narrow scatter
-  const void* pending_host_bases_ = nullptr;  // host bases still to upload (see enqueue)
+  const void* pending_host_bases_ = nullptr;  // host bases still to upload (see upload_pending_bases)
   hipStream_t copy_stream_ = nullptr;
   hipEvent_t copy_done_ = nullptr;
   std::vector<hipEvent_t> chunk_ev_;  // host-resident pipeline: chunk k uploaded
   DeviceBuffer hist_;
   DeviceBuffer rsum_;  // the two-pass G2 window sums' suffix sums (set_variant bit 24)
   DeviceBuffer norm_in_, norm_out_, norm_prefix_;  // affine_bases
-  DeviceBuffer maxlen_, lofs_;  // lofs_: every join level's output offsets
+  DeviceBuffer lofs_;  // every join level's output offsets
   uint32_t* h_max_ = nullptr;  // pinned read-back of the largest bucket
   unsigned last_levels_ = 0;
   size_t last_divisions_ = 1;

@@ -343,7 +343,7 @@ FR29 = LimbField("fr29", gen_fr29.P, 9, 29, 8, {"K16": (16, 1), "K32": (32, 2)},
 # the generators' constants are these
 assert F28.K["K8"] == gen_f28.K8 and F28.K["K32R3"] == gen_f28.K32R3 and F28.PINV == gen_f28.PINV
 assert FR29.K["K32"] == gen_fr29.K32 and FR29.P_HI == gen_fr29.P_HI
-# the base negations of msm_impl.h (repack_y): 33p - y~ << 5 and 257p - y~ << 8
+# the base negations of msm/msm_acc.h (repack_y): 33p - y~ << 5 and 257p - y~ << 8
 NEG_BASE = {"f29": F29.K["K33"], "f28": F28.K["K257"]}
 # curve generators (y^2 = x^3 + 3, y^2 = x^3 + 4)
 GEN = {"f29": (1, 2),

@@ -609,3 +609,53 @@ def test_msm_batch_forced_window_bits(c):
         assert m.run(bases, vecs[7]) == want[7]
     finally:
         m.close()
+
+
+_PROFILE_N = 1 << 12
+_profile_inputs = {}
+
+
+def _profile_case(curve):
+    """n = 2^12 oracle-generated points and the oracle's MSM of them, once per curve."""
+    if curve not in _profile_inputs:
+        bases = O.gen_bases(curve, 91, _PROFILE_N, 64).tobytes()
+        scalars = O.gen_scalars(O.CURVE_INFO[curve][1], 92, _PROFILE_N).tobytes()
+        _profile_inputs[curve] = (bases, scalars, O.msm(curve, bases, scalars)[0])
+    return _profile_inputs[curve]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("curve,c,variant", [
+    ("bn254_g1", 10, 0),                       # segment sums, then the one-launch 29-bit tree
+    ("bn254_g1", 10, 4096),                    # workgroup trees (bit 12)
+    ("bn254_g1", 10, 262144 | (1 << 23)),      # FIPS field, two-level sums (bit 23)
+    ("bn254_g1", 10, 524288),                  # one-launch segment sums + tree (bit 19)
+    ("bn254_g1", 9, 0),                        # B = 256: one scan launch per window
+    ("bn254_g2", 10, 0),                       # lane-pair segment sums
+    ("bn254_g2", 10, 1 << 23),                 # lane-pair two-level sums
+    ("bn254_g2", 10, 1 << 24),                 # lane-pair two-pass sums
+    ("bn254_g1", 10, 4),                       # one window per sort / accumulation group
+])
+def test_msm_profile_marks_every_window_sum_path(curve, c, variant):
+    """The phase marks of a profiled run are all recorded whichever way the
+    window sums are computed: every case runs twice on one context, so a mark
+    that a path leaves out shows as a stale event (a negative phase) or as an
+    error of the elapsed-time query.  The phases lie inside the total."""
+    bases, scalars, want = _profile_case(curve)
+    m = ctx(curve)
+    try:
+        m.set_window_bits(c)
+        m.set_variant(variant)
+        m.set_profile(True)
+        launches = m.plan_windows(_PROFILE_N) if variant == 4 else 1
+        for _ in range(2):
+            assert m.run(bases, scalars) == want
+            t = m.last_timings()
+            assert t["recode"] > 0 and t["acc"] > 0 and t["reduce"] > 0, t
+            assert t["sort"] >= 0, t
+            assert t["total"] >= t["acc"] and t["total"] >= t["reduce"], t
+            assert t["acc_launches"] == launches, t
+    finally:
+        m.set_profile(False)
+        m.set_variant(0)
+        m.set_window_bits(0)
