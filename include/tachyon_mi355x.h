@@ -1244,6 +1244,62 @@ TACHYON_C_EXPORT int tachyon_mi355x_kzg_opening_plan(int curve, int scheme, cons
                                                      const void* values, size_t num_openings, uint64_t* out,
                                                      size_t cap, size_t* out_words);
 
+/* PLONK grand products: the polynomial Z of the Halo2 permutation, lookup and
+ * shuffle arguments (zk/plonk/permutation/grand_product_argument.h:17-122 and
+ * its callers permutation_prover_impl.h:24-86, lookup/halo2/prover_impl.h:
+ * 126-138, shuffle/prover_impl.h:77) on columns that stay in device memory.
+ *
+ * A factor is f(j) = values[j] + m t(j) + c over the rows j < n, with t by
+ * kind: 0 none (the term is dropped), 1 the column `table`, 2 the label
+ * delta^label omega^j of permutation column `label`, computed on the device.
+ * A poly job is a numerator and a denominator factor list: ratio(j) = prod
+ * num(j) / prod den(j), and 0 where the denominator is 0 (the batch inverse's
+ * rule, math/base/groups.h:124-180).  A chain is chain_lens[c] consecutive
+ * jobs of `polys`: z[0] = 1 in its first job and the previous job's
+ * z[usable_rows] in every next one; z[j+1] = z[j] ratio(j) for j <
+ * usable_rows; rows usable_rows+1 .. n-1 receive that job's blinds in order
+ * (zk/base/blinder.h:33-45).  All chains of a call run as one set of four
+ * launches.
+ *
+ * Elements are 32-byte Montgomery values, canonical on output.  Columns and
+ * out_z[i] (n elements per job) are host or device memory; blinds (per job
+ * n - usable_rows - 1 elements, job after job), omega, delta and out_last
+ * (num_chains elements: every chain's final z[usable_rows], or null) are host
+ * memory.  Inputs are never written.
+ *
+ * Returns 1, or 0 with nothing written and no GPU call made when: field is
+ * not 0 (bn254 Fr) or 2 (bls12-381 Fr); n == 0, usable_rows >= n or
+ * n >= 2^31; an array is null with a nonzero count (blinds only when
+ * n - usable_rows - 1 > 0, omega and delta only with a kind-2 factor); a kind
+ * is above 2; a kind-1 factor has no table; a job has no factor at all; an
+ * output overlaps an input column or another output; the call has more than
+ * 2^30 tiles (jobs x ceil(n / tile_rows)).  A HIP failure returns 0 with a
+ * message on stderr; the call never aborts.
+ *
+ * tile_rows: the rows one workgroup owns; walk_tiles: the tile products one
+ * step of the carry walk takes.  last_timings: milliseconds (stream events)
+ * of the last call's passes: ratios, carries, apply. */
+typedef struct {
+  const void* values;
+  const void* table;
+  uint32_t kind;
+  uint32_t label;
+  uint8_t m[32], c[32];
+} tachyon_mi355x_gp_factor;
+typedef struct {
+  const tachyon_mi355x_gp_factor* num;
+  size_t num_count;
+  const tachyon_mi355x_gp_factor* den;
+  size_t den_count;
+} tachyon_mi355x_gp_poly;
+TACHYON_C_EXPORT int tachyon_mi355x_grand_product_chains(int field, size_t n, size_t usable_rows, const void* omega,
+                                                         const void* delta, const tachyon_mi355x_gp_poly* polys,
+                                                         const size_t* chain_lens, size_t num_chains,
+                                                         const void* blinds, void* const* out_z, void* out_last);
+TACHYON_C_EXPORT size_t tachyon_mi355x_grand_product_tile_rows(void);
+TACHYON_C_EXPORT size_t tachyon_mi355x_grand_product_walk_tiles(void);
+TACHYON_C_EXPORT void tachyon_mi355x_grand_product_last_timings(float* out_ms);
+
 /* delete a Jacobian returned by an *_msm / *_msm_gpu entry point (for callers
  * that cannot use C++ delete, e.g. ctypes). */
 TACHYON_C_EXPORT void tachyon_mi355x_jacobian_destroy(int curve, void* jacobian);

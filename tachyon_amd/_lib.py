@@ -216,6 +216,12 @@ SIGNATURES = [
     ("tachyon_mi355x_kzg_opening_plan", i32, [i32, i32, ctypes.POINTER(ctypes.c_size_t), sz, sz,
                                               ctypes.POINTER(ctypes.c_size_t), vp, vp, sz,
                                               ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(ctypes.c_size_t)]),
+    # PLONK grand products (permutation, lookup and shuffle Z)
+    ("tachyon_mi355x_grand_product_chains", i32, [i32, sz, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_size_t), sz, vp,
+                                                  ctypes.POINTER(ctypes.c_void_p), vp]),
+    ("tachyon_mi355x_grand_product_tile_rows", sz, []),
+    ("tachyon_mi355x_grand_product_walk_tiles", sz, []),
+    ("tachyon_mi355x_grand_product_last_timings", None, [fp]),
     # field-generic NTT domains
     ("tachyon_mi355x_ntt_domain_create", vp, [i32, sz]),
     ("tachyon_mi355x_ntt_domain_destroy", None, [vp]),
