@@ -111,6 +111,17 @@ class NttDomain {
   };
   const std::vector<Pass>& plan() const { return plan_; }
 
+  // The 32-bit passes' stage tables of one direction (entry (stage s, index
+  // j) at n - (n >> s) + j): tw = the pass kernel's own entries (BN254 Fr:
+  // Shoup {w, floor(w 2^256 / p)}, 64 B; other fields: twm again), twm = the
+  // Montgomery twiddles.  stage_table_bytes(): the memory of both directions.
+  struct StageTables {
+    const void* tw;
+    const Fr* twm;
+  };
+  StageTables stage_tables(bool inverse) const;
+  size_t stage_table_bytes() const;
+
  private:
   // NttGenDomain's stage tables: the domain of size 2^log_n generated by
   // `group_gen` (any primitive 2^log_n-th root), on the 32-bit passes (no
@@ -139,7 +150,7 @@ class NttDomain {
   DeviceBuffer tw_fwd_, tw_inv_, scratch_, io_;
   DeviceBuffer twm_fwd_, twm_inv_;  // Montgomery twiddles when tw_* hold Shoup entries (BN254 Fr)
   int shoup_mode_ = 2;              // Shoup twiddles: 0 never, 1 every pass, 2 all but the first pass
-  int ntt_variant_ = 0;             // A/B kernel variants (TACHYON_NTT_VARIANT, see run())
+  int ntt_variant_ = 0;             // A/B kernel variants (TACHYON_NTT_VARIANT, see Tables32 in ntt.hip)
   // BN254 Fr: the 29-bit-limb passes and their tables -- R'-form entries for
   // the first pass's stages [0, k0), Shoup entries for the later stages
   int variant_ = 0;
@@ -168,7 +179,8 @@ extern template class NttDomain<Bls381Fr>;
 // entries for the rows >= LN - 20 and Shoup entries for the rows >= LN - 14:
 // the first pass of every L <= 20 covers rows [LN - L, LN - L + k0(L)), the
 // later ones [LN - L + k0(L), LN) with L - k0(L) <= 14.  Each size runs the
-// plan and the kernel variant NttDomain(m) would.
+// plan and the kernel variant NttDomain(m) would, through the pass loop and
+// the PassArgs builder NttDomain uses (ntt.hip, run_passes).
 template <class Fr>
 class NttGenDomain {
  public:
@@ -214,7 +226,6 @@ class NttGenDomain {
   void run32(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const CosetTables* ct);
   void run29(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const CosetTables* ct);
   bool uses29(uint32_t log_m) const;
-  uint32_t pack_log(uint32_t log_m, size_t batch) const;
 
   hipStream_t stream_ = nullptr;
   bool own_stream_ = false;

@@ -1,9 +1,14 @@
-// Radix-2 NTT kernels for MI355X (gfx950) and the NttDomain host driver.
+// Radix-2 NTT for MI355X (gfx950): the host drivers NttDomain, NttGenDomain,
+// Ntt4Step and NttMultiDevice.  Their kernels are in the three headers below,
+// one translation unit with this file; one pass loop (run_passes) launches
+// the passes of every transform.
 // Reference semantics: radix2_evaluation_domain.h:213-333,
 // univariate_evaluation_domain.h:141-232,464-489,518-566, radix2_twiddle_cache.h:57-121.
 #include "ntt.h"
 
-#include "../field/fr29.h"
+#include "ntt_pass32.h"
+#include "ntt_pass29.h"
+#include "ntt_tables.h"
 
 #include <algorithm>
 #include <atomic>
@@ -14,544 +19,6 @@
 namespace tachyon_amd::ntt {
 
 namespace {
-
-constexpr unsigned kBlock = 256;
-constexpr uint32_t kMaxPassStages = 8;
-// Elements per workgroup: 1024 (32 KiB of LDS) = 256 threads x 2^2, so every
-// thread owns one radix-4 group per register step and 5 workgroups fit a CU
-// (5 waves per SIMD at 88 VGPRs).  2^24 sweep (tools/tune_ntt.py,
-// TACHYON_NTT_LDS_ELEMS x TACHYON_NTT_RADIX_LOG): 2048/r3 2.43, 2048/r2 2.44,
-// 1024/r2 1.95, 1024/r3 2.82 (half the threads idle), 512/r2 2.54 ms.
-constexpr uint32_t kMaxLdsElems = 1024;
-
-enum : uint32_t {
-  kLoadCoset = 1,
-  kStoreScale = 2,
-  kStoreCoset = 4,
-  kLoadTw4 = 8,
-  kStoreTw4 = 16,
-  kLoadXch = 32,
-  kStoreXch = 64
-};
-
-// Twiddle tables.  BN254 Fr butterflies multiply by a Shoup product
-// (Fp::mul_shoup, mont_asm.h shoup_mul_8): an entry is the plain twiddle and
-// its quotient floor(w 2^256 / p), 64 bytes -- 13 fewer v_mad_u64_u32, 29
-// fewer carry adds and no Montgomery digits per butterfly than a Montgomery
-// product by a 32-byte Montgomery twiddle.  BLS12-381 Fr (3p > 2^256) keeps
-// Montgomery twiddles.
-template <class Fr>
-struct ShoupTw {
-  Fr w, wq;
-};
-template <class Fr>
-struct NttTw {
-  using type = Fr;
-};
-template <>
-struct NttTw<Bn254Fr> {
-  using type = ShoupTw<Bn254Fr>;
-};
-template <class Fr>
-__device__ __forceinline__ Fr tw_mul(const Fr& x, const Fr& w) {
-  return x * w;
-}
-template <class Fr>
-__device__ __forceinline__ Fr tw_mul(const Fr& x, const ShoupTw<Fr>& t) {
-  return x.mul_shoup(t.w, t.wq);
-}
-
-template <class Fr>
-struct PassArgs {
-  uint32_t L, s0, k, log_m, final_pass, mode, pow_bits;
-  const Fr* load_lo;
-  const Fr* load_hi;
-  const Fr* store_lo;
-  const Fr* store_hi;
-  Fr scale;
-  // four-step exchange (kStoreTw4: the forward stage 1's last pass; kLoadTw4:
-  // the inverse stage 2's first pass): element k of batch entry b (the local
-  // column c_l) times w_N^(+-(c0 + b) k), at its packed send / recv position
-  FourStepTw<Fr> fs;
-  // single-pass transforms smaller than a tile: 2^pack batch entries per
-  // workgroup, set m = entry (blockIdx.y << pack) + m (0: one entry per blockIdx.y)
-  uint32_t pack;
-};
-
-// The exchange layout of the fused stages: chunk h (n/G^2 elements, to / from
-// rank h) holds [k1_l][c_l], row-major -- so the row NTTs read (forward
-// stage 2) and write (inverse stage 1) Cg-element runs and need no transpose.
-// Column side: element k1 of local column c_l at (h Rg + k1_l) Cg + c_l =
-// k1 Cg + c_l (h = k1 >> log_rg).  (The unfused round-4 stages keep
-// twiddle_exchange_kernel's [c_l][k1_l] chunks and the transposes.)
-template <class Fr>
-__device__ __forceinline__ size_t fs_packed(const FourStepTw<Fr>& f, uint32_t k1, uint32_t c_l) {
-  return ((size_t)k1 << f.log_cg) + c_l;
-}
-// Row side: element c (column, c = g Cg + c_l) of local row j at (g Rg + j) Cg + c_l
-template <class Fr>
-__device__ __forceinline__ size_t xch_pos(const FourStepTw<Fr>& f, uint32_t c, uint32_t j) {
-  return ((((size_t)(c >> f.log_cg) << f.log_rg) + j) << f.log_cg) + (c & ((1u << f.log_cg) - 1));
-}
-// w_N^((c0 + c_l) k1) from the two-level power tables of the four-step's root
-template <class Fr>
-__device__ __forceinline__ Fr fs_twiddle(const FourStepTw<Fr>& f, uint32_t k1, uint32_t c_l) {
-  const uint64_t e = ((uint64_t)(f.c0 + c_l) * k1) & ((uint64_t(1) << f.log_n) - 1);
-  return f.lo[e & ((1u << f.bits) - 1)] * f.hi[e >> f.bits];
-}
-
-__device__ __forceinline__ uint32_t bitrev(uint32_t x, uint32_t bits) {
-  return bits == 0 ? 0u : (__brev(x) >> (32 - bits));
-}
-
-// One pass of k DIF stages (s0 .. s0+k-1) over M sets of 2^k elements held in
-// LDS.  Non-final passes are in place (each workgroup reads and writes the
-// same positions); the final pass (s0 + k == L) writes natural order through
-// the bit-reversal permutation, M bit-reversed-consecutive sets per workgroup
-// so every store row is M contiguous elements.
-// R DIF stages (t .. t+R-1 of the pass) on groups of 2^R elements held in
-// registers.  Group g covers set m = g mod M and the positions
-// a0 + j q (j < 2^R, q = 2^(k-t-R)); stage t+u pairs j with j + 2^(R-1-u).
-// Twiddle of the butterfly whose low element has global index i at global
-// stage s: w_s^(i mod 2^(L-s-1)) (the reference's Radix2TwiddleCache row s).
-// kLast: the transform's last R stages (final pass, t + R == k).
-template <int R, bool kLast, bool kPrefetch, class Fr, class Tw, class IndexFn>
-__device__ __forceinline__ void radix_step(Fr* __restrict__ lds, const Tw* __restrict__ tw, const PassArgs<Fr>& a,
-                                           uint32_t t, IndexFn index) {
-  constexpr int E = 1 << R;
-  const uint32_t log_m = a.log_m, M = 1u << log_m;
-  const uint32_t n = 1u << a.L;
-  const uint32_t groups = (M << a.k) >> R;
-  const uint32_t qlog = a.k - t - R;
-  for (uint32_t g = threadIdx.x; g < groups; g += kBlock) {
-    const uint32_t m = g & (M - 1);
-    const uint32_t rr = g >> log_m;
-    const uint32_t off = rr & ((1u << qlog) - 1);
-    const uint32_t a0 = ((rr >> qlog) << (qlog + R)) + off;
-    // the step's twiddles first: their global loads overlap the LDS reads
-    // and the first butterflies instead of stalling each product
-    Tw wv[R][E / 2];
-    if constexpr (!kLast && kPrefetch) {
-#pragma unroll
-      for (int u = 0; u < R; ++u) {
-        const uint32_t st = a.s0 + t + u;
-        const uint32_t gap_mask = (1u << (a.L - st - 1)) - 1;
-        const Tw* tws = tw + (n - (n >> st));
-        const int half = E >> (u + 1);
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-          if (j & half) continue;
-          wv[u][c++] = tws[index(a0 + ((uint32_t)j << qlog), m) & gap_mask];
-        }
-      }
-    }
-    Fr x[E];
-#pragma unroll
-    for (int j = 0; j < E; ++j) x[j] = lds[((a0 + ((uint32_t)j << qlog)) << log_m) + m];
-#pragma unroll
-    for (int u = 0; u < R; ++u) {
-      const uint32_t st = a.s0 + t + u;
-      const Tw* tws = tw + (n - (n >> st));
-      const int half = E >> (u + 1);
-      int c = 0;
-#pragma unroll
-      for (int j = 0; j < E; ++j) {
-        if (j & half) continue;
-        const Fr lo = x[j], hi = x[j + half];
-        // ButterflyFnInOut: lo = lo + hi; hi = (lo - hi) * w
-        x[j] = lo + hi;
-        if constexpr (kLast) {
-          // the transform's last R stages: the twiddle index is j mod 2^(R-1-u)
-          // (a0 and the set base are multiples of 2^R), known at compile time;
-          // index 0 is w = 1 -- the whole last stage and half the one before
-          const uint32_t idx = (uint32_t)j & ((1u << (R - 1 - u)) - 1);
-          x[j + half] = idx ? tw_mul(lo.sub_unreduced(hi), tws[idx]) : (lo - hi);
-        } else {
-          // twiddles are canonical, so lo - hi + 2p needs no borrow test
-          if constexpr (kPrefetch) {
-            x[j + half] = tw_mul(lo.sub_unreduced(hi), wv[u][c++]);
-          } else {
-            const uint32_t gap_mask = (1u << (a.L - st - 1)) - 1;
-            x[j + half] = tw_mul(lo.sub_unreduced(hi), tws[index(a0 + ((uint32_t)j << qlog), m) & gap_mask]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < E; ++j) lds[((a0 + ((uint32_t)j << qlog)) << log_m) + m] = x[j];
-  }
-}
-
-template <class Fr, class Tw, int MaxR, bool kPrefetch = true, int kWaves = 1>
-__global__ __launch_bounds__(kBlock, kWaves) void dif_pass_kernel(const Fr* __restrict__ in, Fr* __restrict__ out,
-                                                          const Tw* __restrict__ tw, PassArgs<Fr> a) {
-  extern __shared__ uint4 smem_raw[];
-  Fr* lds = reinterpret_cast<Fr*>(smem_raw);
-  const uint32_t L = a.L, k = a.k, log_m = a.log_m;
-  const uint32_t M = 1u << log_m;
-  const uint32_t elems = M << k;
-  const uint32_t b = blockIdx.x;
-  // batch of independent contiguous transforms (the packed four-step
-  // layouts address the whole buffer themselves); with a.pack the workgroup's
-  // sets are 2^pack whole transforms, entries ybase + m
-  const uint32_t pk = a.pack, ybase = blockIdx.y << pk;
-  if (!(a.mode & (kLoadTw4 | kLoadXch))) in += (size_t)ybase << L;
-  if (!(a.mode & (kStoreTw4 | kStoreXch))) out += (size_t)ybase << L;
-
-  // index(mid, m) of element m of the block's set, position mid in the set
-  uint32_t hi_shift = L - a.s0;            // set stride in the hi dimension
-  uint32_t mid_shift = L - a.s0 - k;       // stride between set members
-  uint32_t hi = 0, lo_base = 0, r0 = 0;
-  if (!a.final_pass) {
-    uint32_t lo_blocks = (1u << mid_shift) >> log_m;
-    hi = b / lo_blocks;
-    lo_base = (b - hi * lo_blocks) << log_m;
-  } else {
-    r0 = b << log_m;
-  }
-  auto index = [&](uint32_t mid, uint32_t m) -> uint32_t {
-    if (!a.final_pass) return (hi << hi_shift) + (mid << mid_shift) + lo_base + m;
-    uint32_t h = bitrev(r0 + m, L - k);
-    return (h << k) + mid;
-  };
-
-  // ---- load ----
-  for (uint32_t e = threadIdx.x; e < elems; e += kBlock) {
-    uint32_t mid = e >> log_m, m = e & (M - 1);
-    uint32_t i = index(mid, m);
-    const uint32_t ent = pk ? m : 0u;
-    Fr v;
-    if (a.mode & kLoadTw4) {
-      v = in[fs_packed(a.fs, i, ybase + ent)] * fs_twiddle(a.fs, i, ybase + ent);
-    } else if (a.mode & kLoadXch) {
-      v = in[xch_pos(a.fs, i, ybase + ent)];
-    } else {
-      v = in[((size_t)ent << L) + i];
-      if (a.mode & kLoadCoset) v = v * (a.load_lo[i & ((1u << a.pow_bits) - 1)] * a.load_hi[i >> a.pow_bits]);
-    }
-    lds[e] = v;
-  }
-  __syncthreads();
-
-  // ---- k butterfly stages, up to MaxR per LDS round trip ----
-  // A step of R stages loads 2^R elements of one set into registers, runs
-  // the R * 2^(R-1) butterflies there (2^(R-1) independent ones per stage,
-  // which the scheduler interleaves) and writes them back: one LDS round
-  // trip and one barrier per R stages instead of per stage.
-  for (uint32_t t = 0; t < k;) {
-    const uint32_t R = min((uint32_t)MaxR, k - t);
-    const bool last = a.final_pass && t + R == k;
-    if (MaxR >= 3 && R == 3) {
-      if (last) radix_step<3, true, kPrefetch>(lds, tw, a, t, index);
-      else radix_step<3, false, kPrefetch>(lds, tw, a, t, index);
-    } else if (MaxR >= 2 && R == 2) {
-      if (last) radix_step<2, true, kPrefetch>(lds, tw, a, t, index);
-      else radix_step<2, false, kPrefetch>(lds, tw, a, t, index);
-    } else {
-      if (last) radix_step<1, true, kPrefetch>(lds, tw, a, t, index);
-      else radix_step<1, false, kPrefetch>(lds, tw, a, t, index);
-    }
-    t += R;
-    __syncthreads();
-  }
-
-  // ---- store ----
-  if (!a.final_pass) {
-    for (uint32_t e = threadIdx.x; e < elems; e += kBlock) {
-      uint32_t mid = e >> log_m, m = e & (M - 1);
-      out[index(mid, m)] = lds[e];
-    }
-  } else {
-    for (uint32_t e = threadIdx.x; e < elems; e += kBlock) {
-      uint32_t q = e >> log_m, m = e & (M - 1);
-      uint32_t mid = bitrev(q, k);
-      Fr v = lds[(mid << log_m) + m];
-      const uint32_t o = pk ? q : (q << (L - k)) + r0 + m, ent = pk ? m : 0u;
-      if (a.mode & kStoreCoset) v = v * (a.store_lo[o & ((1u << a.pow_bits) - 1)] * a.store_hi[o >> a.pow_bits]);
-      else if (a.mode & kStoreScale) v = v * a.scale;
-      if (a.mode & kStoreTw4) out[fs_packed(a.fs, o, ybase + ent)] = (v * fs_twiddle(a.fs, o, ybase + ent)).canonical();
-      else if (a.mode & kStoreXch) out[xch_pos(a.fs, o, ybase + ent)] = v.canonical();
-      else out[((size_t)ent << L) + o] = v.canonical();
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// BN254 Fr passes over 9 x 29-bit limbs (field/fr29.h): the same DIF network,
-// pass plan, index maps, bit reversal and fused scalings as dif_pass_kernel,
-// with the butterflies of fr29::radix4 / radix2 (carry-free products, limb-wise
-// sums and differences).  Elements between passes are 36-byte F29 (normalized,
-// < 8p); the first pass reads the 32-byte Montgomery input, the final pass
-// writes canonical 32-byte values.  LDS holds the elements as 9 limb planes
-// of kMaxLdsElems words (a plane stride fixed at compile time: one ds_read_b32
-// per limb with an immediate offset).  Twiddles: R'-form (36 B) in the first
-// pass, whose stage tables stream from HBM; Shoup (72 B) in the later ones.
-using fr29::F29;
-template <class TwT>
-struct Tw29Table {
-  const TwT* tw;  // entry of (stage s, index j) at tw[(n - (n >> s)) - off + j]
-  uint32_t off;
-};
-
-// kSwz: positions XOR-swizzled so that the 32-lane groups of a ds_read_b32 /
-// ds_write_b32 (bank = word mod 32) hit 32 distinct banks in every register
-// step of the 8-stage, 4-set passes (2^24: qlog = 6, 4, 2, 0): bit 2 ^= bit 5,
-// bits 3, 4 ^= bit 6.  Without it the qlog = 2 / 0 steps are 2- / 4-way
-// conflicted on all 72 LDS accesses of a group.
-template <bool kSwz>
-__device__ __forceinline__ uint32_t swz29(uint32_t p) {
-  if constexpr (kSwz) return p ^ ((p >> 3) & 4u) ^ (((p >> 6) & 1u) * 0x18u);
-  else return p;
-}
-template <bool kSwz>
-__device__ __forceinline__ F29 lds29_load(const uint32_t* __restrict__ lds, uint32_t pos) {
-  F29 v;
-  pos = swz29<kSwz>(pos);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) v.l[i] = lds[i * kMaxLdsElems + pos];
-  return v;
-}
-template <bool kSwz>
-__device__ __forceinline__ void lds29_store(uint32_t* __restrict__ lds, uint32_t pos, const F29& v) {
-  pos = swz29<kSwz>(pos);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) lds[i * kMaxLdsElems + pos] = v.l[i];
-}
-
-template <int R, bool kLast, bool kSwz, class TwT, class IndexFn>
-__device__ __forceinline__ void radix29_step(uint32_t* __restrict__ lds, Tw29Table<TwT> tt,
-                                             const PassArgs<Bn254Fr>& a, uint32_t t, IndexFn index) {
-  constexpr int E = 1 << R;
-  const uint32_t log_m = a.log_m, M = 1u << log_m;
-  const uint32_t n = 1u << a.L;
-  const uint32_t groups = (M << a.k) >> R;
-  const uint32_t qlog = a.k - t - R;
-  const uint32_t st = a.s0 + t;
-  const TwT* twA = tt.tw + ((n - (n >> st)) - tt.off);
-  const uint32_t gapA = (1u << (a.L - st - 1)) - 1;
-  for (uint32_t g = threadIdx.x; g < groups; g += kBlock) {
-    const uint32_t m = g & (M - 1);
-    const uint32_t rr = g >> log_m;
-    const uint32_t off = rr & ((1u << qlog) - 1);
-    const uint32_t a0 = ((rr >> qlog) << (qlog + R)) + off;
-    if constexpr (R == 2) {
-      // twiddles first: their loads overlap the LDS reads
-      TwT tA0, tA1, tB0, tB1;
-      if constexpr (kLast) {
-        tA1 = twA[1];  // stage L - 2 has the two entries {1, w_4}; everything else is 1
-      } else {
-        const TwT* twB = tt.tw + ((n - (n >> (st + 1))) - tt.off);
-        const uint32_t gapB = (1u << (a.L - st - 2)) - 1;
-        tA0 = twA[index(a0, m) & gapA];
-        tA1 = twA[index(a0 + (1u << qlog), m) & gapA];
-        tB0 = twB[index(a0, m) & gapB];
-        tB1 = twB[index(a0 + (2u << qlog), m) & gapB];
-      }
-      F29 x[4];
-#pragma unroll
-      for (int j = 0; j < E; ++j) x[j] = lds29_load<kSwz>(lds, ((a0 + ((uint32_t)j << qlog)) << log_m) + m);
-      if constexpr (kLast) fr29::radix4_last(x, tA1);
-      else fr29::radix4(x, tA0, tA1, tB0, tB1);
-#pragma unroll
-      for (int j = 0; j < E; ++j) lds29_store<kSwz>(lds, ((a0 + ((uint32_t)j << qlog)) << log_m) + m, x[j]);
-    } else {
-      TwT tA;
-      if constexpr (!kLast) tA = twA[index(a0, m) & gapA];
-      F29 x[2];
-#pragma unroll
-      for (int j = 0; j < E; ++j) x[j] = lds29_load<kSwz>(lds, ((a0 + ((uint32_t)j << qlog)) << log_m) + m);
-      if constexpr (kLast) fr29::radix2_last(x);
-      else fr29::radix2(x, tA);
-#pragma unroll
-      for (int j = 0; j < E; ++j) lds29_store<kSwz>(lds, ((a0 + ((uint32_t)j << qlog)) << log_m) + m, x[j]);
-    }
-  }
-}
-
-// kFirst: the input is the 32-byte Montgomery array (the transform's first
-// pass, R'-form twiddles); otherwise 36-byte F29 from the previous pass.
-template <bool kFirst, bool kSwz, class TwT>
-__global__ __launch_bounds__(kBlock) void dif29_pass_kernel(const void* __restrict__ in_v, void* __restrict__ out_v,
-                                                            Tw29Table<TwT> tt, PassArgs<Bn254Fr> a) {
-  __shared__ uint32_t lds[9 * kMaxLdsElems];
-  const uint32_t L = a.L, k = a.k, log_m = a.log_m;
-  const uint32_t M = 1u << log_m;
-  const uint32_t elems = M << k;
-  const uint32_t b = blockIdx.x;
-  uint32_t hi_shift = L - a.s0;
-  uint32_t mid_shift = L - a.s0 - k;
-  uint32_t hi = 0, lo_base = 0, r0 = 0;
-  if (!a.final_pass) {
-    uint32_t lo_blocks = (1u << mid_shift) >> log_m;
-    hi = b / lo_blocks;
-    lo_base = (b - hi * lo_blocks) << log_m;
-  } else {
-    r0 = b << log_m;
-  }
-  auto index = [&](uint32_t mid, uint32_t m) -> uint32_t {
-    if (!a.final_pass) return (hi << hi_shift) + (mid << mid_shift) + lo_base + m;
-    uint32_t h = bitrev(r0 + m, L - k);
-    return (h << k) + mid;
-  };
-
-  // ---- load ----
-  // (a.pack: the workgroup's sets are 2^pack whole transforms, entries ybase + m)
-  const uint32_t pk = a.pack, ybase = blockIdx.y << pk;
-  const size_t batch_off = (size_t)ybase << L;
-  for (uint32_t e = threadIdx.x; e < elems; e += kBlock) {
-    const uint32_t mid = e >> log_m, m = e & (M - 1);
-    const uint32_t i = index(mid, m);
-    const uint32_t ent = pk ? m : 0u;
-    F29 v;
-    if constexpr (kFirst) {
-      Bn254Fr x;
-      if ((a.mode & kLoadTw4) && a.fs.tab29) {  // the precomputed R'-form twiddle: one product
-        const Bn254Fr raw = static_cast<const Bn254Fr*>(in_v)[fs_packed(a.fs, i, ybase + ent)];
-        const auto* t29 = static_cast<const fr29::TwMont29*>(a.fs.tab29);
-        v = fr29::tw_prod(fr29::from_words(raw.v), t29[((size_t)(ybase + ent) << a.fs.log_r) + i]);
-        lds29_store<kSwz>(lds, e, v);
-        continue;
-      }
-      if (a.mode & kLoadTw4) {
-        x = static_cast<const Bn254Fr*>(in_v)[fs_packed(a.fs, i, ybase + ent)] * fs_twiddle(a.fs, i, ybase + ent);
-      } else if (a.mode & kLoadXch) {
-        x = static_cast<const Bn254Fr*>(in_v)[xch_pos(a.fs, i, ybase + ent)];
-      } else {
-        x = static_cast<const Bn254Fr*>(in_v)[batch_off + ((size_t)ent << L) + i];
-        if (a.mode & kLoadCoset) x = x * (a.load_lo[i & ((1u << a.pow_bits) - 1)] * a.load_hi[i >> a.pow_bits]);
-      }
-      v = fr29::from_words(x.v);
-    } else {
-      v = static_cast<const F29*>(in_v)[batch_off + ((size_t)ent << L) + i];
-    }
-    lds29_store<kSwz>(lds, e, v);
-  }
-  __syncthreads();
-
-  for (uint32_t t = 0; t < k;) {
-    const uint32_t R = min(2u, k - t);
-    const bool last = a.final_pass && t + R == k;
-    if (R == 2) {
-      if (last) radix29_step<2, true, kSwz>(lds, tt, a, t, index);
-      else radix29_step<2, false, kSwz>(lds, tt, a, t, index);
-    } else {
-      if (last) radix29_step<1, true, kSwz>(lds, tt, a, t, index);
-      else radix29_step<1, false, kSwz>(lds, tt, a, t, index);
-    }
-    t += R;
-    __syncthreads();
-  }
-
-  // ---- store ----
-  if (!a.final_pass) {
-    F29* out = static_cast<F29*>(out_v) + batch_off;
-    for (uint32_t e = threadIdx.x; e < elems; e += kBlock) {
-      const uint32_t mid = e >> log_m, m = e & (M - 1);
-      out[index(mid, m)] = lds29_load<kSwz>(lds, e);
-    }
-  } else {
-    Bn254Fr* out = static_cast<Bn254Fr*>(out_v) + ((a.mode & (kStoreTw4 | kStoreXch)) ? 0 : batch_off);
-    for (uint32_t e = threadIdx.x; e < elems; e += kBlock) {
-      const uint32_t q = e >> log_m, m = e & (M - 1);
-      const uint32_t mid = bitrev(q, k);
-      Bn254Fr v;
-      const uint32_t o = pk ? q : (q << (L - k)) + r0 + m, ent = pk ? m : 0u;
-      if ((a.mode & kStoreTw4) && a.fs.tab29) {  // the precomputed R'-form twiddle: one product
-        const auto* t29 = static_cast<const fr29::TwMont29*>(a.fs.tab29);
-        const F29 y = fr29::tw_prod(lds29_load<kSwz>(lds, (mid << log_m) + m),
-                                    t29[((size_t)(ybase + ent) << a.fs.log_r) + o]);
-        fr29::to_canonical_words(y, v.v);
-        out[fs_packed(a.fs, o, ybase + ent)] = v;
-        continue;
-      }
-      fr29::to_canonical_words(lds29_load<kSwz>(lds, (mid << log_m) + m), v.v);
-      if (a.mode & kStoreCoset) v = (v * (a.store_lo[o & ((1u << a.pow_bits) - 1)] * a.store_hi[o >> a.pow_bits])).canonical();
-      else if (a.mode & kStoreScale) v = (v * a.scale).canonical();
-      if (a.mode & kStoreTw4) out[fs_packed(a.fs, o, ybase + ent)] = (v * fs_twiddle(a.fs, o, ybase + ent)).canonical();
-      else if (a.mode & kStoreXch) out[xch_pos(a.fs, o, ybase + ent)] = v;
-      else out[((size_t)ent << L) + o] = v;
-    }
-  }
-}
-
-// Montgomery twiddles (canonical w 2^256 mod p) -> the 29-bit tables: entries
-// [0, split) R'-form (w 2^261 mod p = 32 W mod p), entries [split, count)
-// Shoup {w, floor(w 2^261 / p)} with floor(w 2^261 / p) = 32 floor(w 2^256 /
-// p) + floor(32 W / p) (W = w 2^256 mod p, the Montgomery entry).
-__global__ __launch_bounds__(kBlock) void tw29_table_kernel(fr29::TwMont29* __restrict__ mont29,
-                                                            fr29::TwShoup29* __restrict__ shoup29,
-                                                            const Bn254Fr* __restrict__ in, uint32_t split,
-                                                            uint32_t count) {
-  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= count) return;
-  const Bn254Fr W = in[j].canonical();
-  if (j < split) {
-    Bn254Fr x = W;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) x = (x + x).canonical();
-    mont29[j].w = fr29::from_words(x.v);
-  } else {
-    const Bn254Fr w = W.from_mont();
-    const Bn254Fr q32 = Bn254Fr::shoup_quotient(w);
-    // t = floor(32 W / p): five doublings of W (< p, so 2r < 2p < 2^256),
-    // each followed by a subtraction of p when 2r >= p (one quotient bit)
-    uint32_t t = 0;
-    uint32_t r[8];
-    for (int i = 0; i < 8; ++i) r[i] = W.v[i];
-    for (int bit = 0; bit < 5; ++bit) {
-      uint32_t c = 0;
-      for (int i = 0; i < 8; ++i) {
-        const uint32_t nc = r[i] >> 31;
-        r[i] = (r[i] << 1) | c;
-        c = nc;
-      }
-      uint32_t d[8], borrow = 0;
-      for (int i = 0; i < 8; ++i) {
-        const uint64_t s = (uint64_t)r[i] - fr29::kPWords[i] - borrow;
-        d[i] = (uint32_t)s;
-        borrow = (uint32_t)(s >> 63);
-      }
-      t = 2 * t + (borrow ? 0u : 1u);
-      if (!borrow)
-        for (int i = 0; i < 8; ++i) r[i] = d[i];
-    }
-    fr29::TwShoup29 e;
-    e.w = fr29::from_words(w.v);
-    e.wq = f29::shl5_repack(q32.v);
-    e.wq.l[0] |= t;  // the low 5 bits of 32 q32 are zero
-    shoup29[j - split] = e;
-  }
-}
-
-// T0[j] = w^j for j < n/2 from two small power tables: lo[j & mask] * hi[j >> bits]
-template <class Fr>
-__global__ __launch_bounds__(kBlock) void twiddle_base_kernel(Fr* __restrict__ t0, uint32_t count,
-                                                              const Fr* __restrict__ lo, const Fr* __restrict__ hi,
-                                                              uint32_t bits) {
-  uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= count) return;
-  t0[j] = (lo[j & ((1u << bits) - 1)] * hi[j >> bits]).canonical();  // canonical: see radix_step
-}
-
-// Montgomery twiddle table -> Shoup entries {plain w, floor(w 2^256 / p)}
-template <class Fr>
-__global__ __launch_bounds__(kBlock) void shoup_table_kernel(ShoupTw<Fr>* __restrict__ out,
-                                                             const Fr* __restrict__ in, uint32_t count) {
-  uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= count) return;
-  const Fr w = in[j].from_mont();
-  out[j] = ShoupTw<Fr>{w, Fr::shoup_quotient(w)};
-}
-
-// T_s[j] = T_0[j << s]  (the strided sub-sampling of radix2_twiddle_cache.h:105-117)
-template <class T>
-__global__ __launch_bounds__(kBlock) void twiddle_stage_kernel(T* __restrict__ ts, const T* __restrict__ t0,
-                                                               uint32_t count, uint32_t s) {
-  uint32_t j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= count) return;
-  ts[j] = t0[(size_t)j << s];
-}
 
 template <class Fr>
 Fr fr_from_u64(uint64_t v) {
@@ -618,79 +85,173 @@ std::vector<Fr> host_powers(const Fr& base, const Fr& scale, size_t count) {
   return out;
 }
 
-// FourStepTw::tab29: entry (c_l << log_r) + k1 = w_N^((c0 + c_l) k1) of this
-// rank (the direction's power tables in f) in R'-form (32 W mod p, W the
-// canonical Montgomery value: five doublings, as tw29_table_kernel)
-__global__ __launch_bounds__(kBlock) void fs_table29_kernel(FourStepTw<Bn254Fr> f, uint32_t log_r, size_t count,
-                                                            fr29::TwMont29* __restrict__ out) {
-  const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
-  if (j >= count) return;
-  const uint32_t c_l = (uint32_t)(j >> log_r), k1 = (uint32_t)(j & ((size_t(1) << log_r) - 1));
-  Bn254Fr x = fs_twiddle(f, k1, c_l).canonical();
-#pragma unroll
-  for (int i = 0; i < 5; ++i) x = (x + x).canonical();
-  out[j].w = fr29::from_words(x.v);
+// ---------------------------------------------------------------------------
+// The pass driver: every transform of NttDomain and NttGenDomain is one call
+// of run_passes with the tables (32-bit or 29-bit) its passes read.
+
+// A one-pass transform (<= 8 stages) smaller than a tile of kMaxLdsElems: 2^p
+// batch entries per workgroup (the largest p with 2^p | batch and 2^(log_m + p)
+// elements in the tile) instead of one entry using 2^log_m / 4 of its 256
+// threads -- the 2^8-point column NTTs of the four-step's 2^8 x 2^16 split.
+uint32_t pack_log(size_t passes, uint32_t log_m, size_t batch) {
+  if (passes != 1 || batch < 2) return 0;
+  uint32_t p = 0;
+  while (batch % (size_t(2) << p) == 0 && ((size_t(1) << log_m) << (p + 1)) <= kMaxLdsElems) ++p;
+  return p;
 }
 
-// out[c][r] = in[r][c] for a rows x cols row-major matrix, through 32 x 32 LDS tiles
+// The two-level power tables of a coset offset: lo / hi of the forward load,
+// ilo / ihi of the inverse store (the size's inverse included)
 template <class Fr>
-__global__ __launch_bounds__(kBlock) void transpose_kernel(const Fr* __restrict__ in, Fr* __restrict__ out,
-                                                           uint32_t rows, uint32_t cols) {
-  __shared__ Fr tile[32][33];
-  const uint32_t c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-  const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  for (uint32_t j = ty; j < 32; j += 8) {
-    const uint32_t r = r0 + j, c = c0 + tx;
-    if (r < rows && c < cols) tile[j][tx] = in[(size_t)r * cols + c];
+struct CosetPtrs {
+  const Fr* lo;
+  const Fr* hi;
+  const Fr* ilo;
+  const Fr* ihi;
+};
+
+// PassArgs of pass `ps` of a 2^L-point transform (first: its first pass).
+// c = the coset's power tables (null: the plain domain), fs = the four-step
+// exchange fused into the first / last pass (null: the batched layout)
+template <class Fr, class Pass>
+PassArgs<Fr> pass_args(const Pass& ps, uint32_t L, bool first, bool inverse, const Fr& size_inv,
+                       const CosetPtrs<Fr>* c, const FourStepTw<Fr>* fs, uint32_t pack) {
+  PassArgs<Fr> a{};
+  a.L = L;
+  a.s0 = ps.s0;
+  a.k = ps.k;
+  a.log_m = pack ? pack : ps.log_m;
+  a.final_pass = ps.final_pass ? 1u : 0u;
+  a.pow_bits = (L + 1) / 2;
+  a.mode = 0;
+  if (first && !inverse && c) {
+    a.mode |= kLoadCoset;
+    a.load_lo = c->lo;
+    a.load_hi = c->hi;
   }
-  __syncthreads();
-  for (uint32_t j = ty; j < 32; j += 8) {
-    const uint32_t c = c0 + j, r = r0 + tx;
-    if (r < rows && c < cols) out[(size_t)c * rows + r] = tile[tx][j];
+  if (ps.final_pass && inverse) {
+    if (c) {
+      a.mode |= kStoreCoset;
+      a.store_lo = c->ilo;
+      a.store_hi = c->ihi;
+    } else {
+      a.mode |= kStoreScale;
+      a.scale = size_inv;
+    }
   }
+  if (fs) {
+    a.fs = *fs;
+    if (fs->rows) {
+      if (first && !inverse) a.mode |= kLoadXch;
+      if (ps.final_pass && inverse) a.mode |= kStoreXch;
+    } else {
+      if (first && inverse) a.mode |= kLoadTw4;
+      if (ps.final_pass && !inverse) a.mode |= kStoreTw4;
+    }
+  }
+  a.pack = pack;
+  return a;
 }
 
-// forward: send[(h * Cg + c_l) * Rg + k1_l] = work[c_l * R + k1] * w^((c0 + c_l) k1), k1 = h Rg + k1_l
-// inverse (unpack = true): out[c_l * R + k1] = recv[(h * Cg + c_l) * Rg + k1_l] * w^-((c0 + c_l) k1)
+// The stage tables of the 32-bit passes (dif_pass_kernel) in one direction.
+// Shoup twiddles (64 B) in the passes whose stage tables are small and
+// cache-resident; Montgomery twiddles (32 B) where the tables stream from HBM
+// -- the first pass reads the big tables of stages 0.. once each.
 template <class Fr>
-__global__ __launch_bounds__(kBlock) void twiddle_exchange_kernel(const Fr* __restrict__ in, Fr* __restrict__ out,
-                                                                  uint32_t log_r, uint32_t log_rg, uint32_t log_cg,
-                                                                  uint32_t c0, uint32_t log_n, const Fr* __restrict__ lo,
-                                                                  const Fr* __restrict__ hi, uint32_t pow_bits,
-                                                                  uint32_t unpack) {
-  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;  // position in the [c_l][k1] view
-  if (i >= ((size_t)1 << (log_cg + log_r))) return;
-  const uint32_t c_l = (uint32_t)(i >> log_r), k1 = (uint32_t)(i & ((1u << log_r) - 1));
-  const uint32_t h = k1 >> log_rg, k1_l = k1 & ((1u << log_rg) - 1);
-  const size_t j = (((size_t)h << log_cg) + c_l) * ((size_t)1 << log_rg) + k1_l;  // packed position
-  const uint64_t e = ((uint64_t)(c0 + c_l) * k1) & ((uint64_t(1) << log_n) - 1);
-  const Fr w = lo[e & ((1u << pow_bits) - 1)] * hi[e >> pow_bits];
-  if (!unpack) out[j] = in[i] * w;
-  else out[i] = in[j] * w;
-}
+struct Tables32 {
+  using Tw = typename NttTw<Fr>::type;
+  static constexpr bool kShoup = !std::is_same_v<Tw, Fr>;
+  const Tw* tw;        // the Shoup entries (fields without them: the Montgomery tables, as twm)
+  const Fr* twm;       // the Montgomery twiddles
+  int shoup_mode = 2;  // Shoup twiddles: 0 never, 1 every pass, 2 all but the first pass
+  // tuning builds only: DIF stages per register step, and the A/B kernels (bit
+  // 0 = the Montgomery radix-4 pass at >= 5 waves/SIMD, bit 1 = the Shoup
+  // radix-4 passes without the twiddle prefetch at >= 5 waves/SIMD)
+  int radix = 2, ab = 0;
 
-// The two-level power tables of a coset offset, built on the device (no host
-// vector, copy or synchronisation): thread i < lo_cnt writes lo[i] = scale
-// base^i, thread lo_cnt + j writes hi[j] = base^(j 2^bits) (j < hi_cnt), each
-// by square-and-multiply over its exponent (< 2^30).  Canonical values -- the
-// field elements NttDomain::build_powers uploads.
-template <class Fr>
-__global__ __launch_bounds__(kBlock) void coset_powers_kernel(Fr* __restrict__ lo, Fr* __restrict__ hi, Fr base,
-                                                              Fr scale, uint32_t bits, uint32_t lo_cnt,
-                                                              uint32_t hi_cnt) {
-  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= lo_cnt + hi_cnt) return;
-  const bool high = t >= lo_cnt;
-  uint32_t e = high ? (t - lo_cnt) << bits : t;
-  Fr acc = high ? Fr::one() : scale;
-  Fr b = base;
-  while (e) {
-    if (e & 1) acc = acc * b;
-    e >>= 1;
-    if (e) b = b.sqr();
+  void launch(size_t p, dim3 grid, uint32_t elems, hipStream_t stream, const void* src, void* dst,
+              const PassArgs<Fr>& a) const {
+    const Fr* in = static_cast<const Fr*>(src);
+    Fr* out = static_cast<Fr*>(dst);
+    const size_t lds = (size_t)elems * sizeof(Fr);
+    const bool shoup = kShoup && (shoup_mode == 1 || (shoup_mode == 2 && p > 0));
+#ifdef TACHYON_TUNING_KNOBS
+    // tiles above 64 KiB (TACHYON_NTT_LDS_ELEMS > 2048) need the kernel's dynamic-LDS limit raised
+    auto allow = [&](const void* k) {
+      if (lds > 64 * 1024) TA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    };
+    if (shoup) {
+      auto kern = radix == 1 ? dif_pass_kernel<Fr, Tw, 1> : radix == 2 ? dif_pass_kernel<Fr, Tw, 2>
+                                                                       : dif_pass_kernel<Fr, Tw, 3>;
+      if (radix == 2 && (ab & 2)) kern = dif_pass_kernel<Fr, Tw, 2, false, 5>;
+      allow(reinterpret_cast<const void*>(kern));
+      hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, stream, in, out, tw, a);
+    } else {
+      auto kern = radix == 1 ? dif_pass_kernel<Fr, Fr, 1> : radix == 2 ? dif_pass_kernel<Fr, Fr, 2>
+                                                                       : dif_pass_kernel<Fr, Fr, 3>;
+      if (radix == 2 && (ab & 1)) kern = dif_pass_kernel<Fr, Fr, 2, true, 5>;
+      allow(reinterpret_cast<const void*>(kern));
+      hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, stream, in, out, twm, a);
+    }
+#else
+    // release schedule: radix-4 register steps (2 DIF stages per LDS round trip)
+    if (lds > 64 * 1024) throw std::runtime_error("tachyon_mi355x: NTT pass tile above 64 KiB in a release build");
+    if (shoup) hipLaunchKernelGGL((dif_pass_kernel<Fr, Tw, 2>), grid, dim3(kBlock), lds, stream, in, out, tw, a);
+    else hipLaunchKernelGGL((dif_pass_kernel<Fr, Fr, 2>), grid, dim3(kBlock), lds, stream, in, out, twm, a);
+#endif
   }
-  if (high) hi[t - lo_cnt] = acc.canonical();
-  else lo[t] = acc.canonical();
+};
+
+// The tables of the 29-bit passes (dif29_pass_kernel, BN254 Fr) in one
+// direction: R'-form entries for the first pass, Shoup entries (the stage
+// tables from entry ts_off on) for the later ones.  Elements between passes
+// are 36-byte F29: the scratch of these passes holds batch * 2^L of them.
+// (Fr = Bn254Fr.  A template so that its kernels are instantiated with its
+// callers, after Tables32's: the order of the kernels in the code object.)
+template <class Fr>
+struct Tables29 {
+  const fr29::TwMont29* tm;
+  const fr29::TwShoup29* ts;
+  uint32_t ts_off;
+  bool swizzle;  // XOR-swizzled LDS positions (swz29)
+
+  void launch(size_t p, dim3 grid, uint32_t elems, hipStream_t stream, const void* src, void* dst,
+              const PassArgs<Fr>& a) const {
+    // the kernel's LDS planes are sized for kMaxLdsElems (tuning plans with larger tiles: 32-bit only)
+    if (elems > kMaxLdsElems) throw std::runtime_error("tachyon_mi355x: 29-bit NTT pass tile above its LDS planes");
+    if (p == 0) {
+      auto* k0 = swizzle ? &dif29_pass_kernel<true, true, fr29::TwMont29> : &dif29_pass_kernel<true, false, fr29::TwMont29>;
+      hipLaunchKernelGGL(k0, grid, dim3(kBlock), 0, stream, src, dst, Tw29Table<fr29::TwMont29>{tm, 0u}, a);
+    } else {
+      auto* k1 = swizzle ? &dif29_pass_kernel<false, true, fr29::TwShoup29>
+                         : &dif29_pass_kernel<false, false, fr29::TwShoup29>;
+      hipLaunchKernelGGL(k1, grid, dim3(kBlock), 0, stream, src, dst, Tw29Table<fr29::TwShoup29>{ts, ts_off}, a);
+    }
+  }
+};
+
+// The passes of `plan` over `batch` arrays of 2^L elements, enqueued on
+// `stream`: the first pass reads src (null: data), the middle passes work in
+// place on scratch, the final pass writes data -- a one-pass transform never
+// touches scratch.  ev (null: no profile): plan.size() + 1 events, recorded
+// before the first pass and after each one.
+template <class Fr, class Tables, class Pass>
+void run_passes(const Tables& tables, const std::vector<Pass>& plan, uint32_t L, bool inverse, size_t batch,
+                uint32_t pack, const Fr& size_inv, const CosetPtrs<Fr>* coset, const FourStepTw<Fr>* fs,
+                const Fr* src, Fr* data, void* scratch, hipStream_t stream, const hipEvent_t* ev) {
+  if (ev) TA_HIP(hipEventRecord(ev[0], stream));
+  for (size_t p = 0; p < plan.size(); ++p) {
+    const Pass& ps = plan[p];
+    const PassArgs<Fr> a = pass_args(ps, L, p == 0, inverse, size_inv, coset, fs, pack);
+    const void* in = p == 0 ? static_cast<const void*>(src ? src : data) : scratch;
+    void* out = ps.final_pass ? static_cast<void*>(data) : scratch;
+    const uint32_t elems = (1u << a.log_m) << ps.k;
+    const uint32_t blocks = pack ? 1u : (uint32_t)((size_t(1) << L) / elems);
+    const uint32_t gy = (uint32_t)(batch >> pack);
+    tables.launch(p, dim3(blocks, gy), elems, stream, in, out, a);
+    TA_HIP(hipGetLastError());
+    if (ev) TA_HIP(hipEventRecord(ev[p + 1], stream));
+  }
 }
 
 }  // namespace
@@ -871,17 +432,22 @@ bool NttDomain<Fr>::set_variant(int v) {
   return true;
 }
 
-// A one-pass transform (<= 8 stages) smaller than a tile of kMaxLdsElems: 2^p
-// batch entries per workgroup (the largest p with 2^p | batch and 2^(L + p)
-// elements in the tile) instead of one entry using 2^L / 4 of its 256 threads
-// -- the 2^8-point column NTTs of the four-step's 2^8 x 2^16 split.  Variant
-// bit 2 turns it off (A/B).
+// Variant bit 2 turns the packing of one-pass transforms off (A/B)
 template <class Fr>
 uint32_t NttDomain<Fr>::pack_log(size_t batch) const {
-  if (plan_.size() != 1 || batch < 2 || (variant_ & 4)) return 0;
-  uint32_t p = 0;
-  while (batch % (size_t(2) << p) == 0 && (n_ << (p + 1)) <= kMaxLdsElems) ++p;
-  return p;
+  return (variant_ & 4) ? 0 : ntt::pack_log(plan_.size(), log_n_, batch);
+}
+
+template <class Fr>
+typename NttDomain<Fr>::StageTables NttDomain<Fr>::stage_tables(bool inverse) const {
+  const DeviceBuffer& tw = inverse ? tw_inv_ : tw_fwd_;
+  const DeviceBuffer& twm = inverse ? twm_inv_ : twm_fwd_;
+  return {tw.as<void>(), Tables32<Fr>::kShoup ? twm.as<Fr>() : tw.as<Fr>()};
+}
+
+template <class Fr>
+size_t NttDomain<Fr>::stage_table_bytes() const {
+  return tw_fwd_.capacity() + tw_inv_.capacity() + twm_fwd_.capacity() + twm_inv_.capacity();
 }
 
 template <class Fr>
@@ -922,98 +488,16 @@ void NttDomain<Fr>::run(Fr* d_data, bool inverse, size_t batch, const Fr* src_in
     return;
   }
   if (batch > 65535) throw std::runtime_error("tachyon_mi355x: NTT batch exceeds the grid limit");
-  if constexpr (std::is_same_v<Fr, Bn254Fr>) {
-    if (variant_ & 1) return run29(d_data, inverse, batch, src_in, fs);
-  }
-  using Tw = typename NttTw<Fr>::type;
-  constexpr bool kShoup = !std::is_same_v<Tw, Fr>;
-  const Tw* tw = inverse ? tw_inv_.as<Tw>() : tw_fwd_.as<Tw>();
-  const Fr* twm = kShoup ? (inverse ? twm_inv_.as<Fr>() : twm_fwd_.as<Fr>()) : reinterpret_cast<const Fr*>(tw);
-  Fr* scratch = plan_.size() > 1 ? static_cast<Fr*>(scratch_.ensure(batch * n_ * sizeof(Fr))) : d_data;
-  if (profile_) TA_HIP(hipEventRecord(ev_[0], stream_));
-  for (size_t p = 0; p < plan_.size(); ++p) {
-    const Pass& ps = plan_[p];
-    PassArgs<Fr> a{};
-    a.L = log_n_;
-    a.s0 = ps.s0;
-    a.k = ps.k;
-    a.log_m = ps.log_m;
-    a.final_pass = ps.final_pass ? 1u : 0u;
-    a.pow_bits = pow_bits_;
-    a.mode = 0;
-    if (p == 0 && !inverse && has_offset_) {
-      a.mode |= kLoadCoset;
-      a.load_lo = coset_lo_.as<Fr>();
-      a.load_hi = coset_hi_.as<Fr>();
-    }
-    if (ps.final_pass && inverse) {
-      if (has_offset_) {
-        a.mode |= kStoreCoset;
-        a.store_lo = icoset_lo_.as<Fr>();
-        a.store_hi = icoset_hi_.as<Fr>();
-      } else {
-        a.mode |= kStoreScale;
-        a.scale = size_inv_;
-      }
-    }
-    if (fs) {
-      a.fs = *fs;
-      if (fs->rows) {
-        if (p == 0 && !inverse) a.mode |= kLoadXch;
-        if (ps.final_pass && inverse) a.mode |= kStoreXch;
-      } else {
-        if (p == 0 && inverse) a.mode |= kLoadTw4;
-        if (ps.final_pass && !inverse) a.mode |= kStoreTw4;
-      }
-    }
-    // first pass: data (or src_in) -> scratch; middle: scratch in place; last: scratch -> data
-    const Fr* src = (p == 0) ? (src_in ? src_in : d_data) : scratch;
-    Fr* dst = ps.final_pass ? d_data : scratch;
-    // a one-pass transform smaller than a tile: several batch entries per workgroup
-    a.pack = pack_log(batch);
-    if (a.pack) a.log_m = a.pack;
-    uint32_t elems = (1u << a.log_m) << ps.k;
-    uint32_t blocks = a.pack ? 1u : (uint32_t)(n_ / elems);
-    const uint32_t gy = (uint32_t)(batch >> a.pack);
-    size_t lds = (size_t)elems * sizeof(Fr);
-    // Shoup twiddles (64 B) in the passes whose stage tables are small and
-    // cache-resident; Montgomery twiddles (32 B) where the tables stream from
-    // HBM -- the first pass reads the big tables of stages 0.. once each
-    // (TACHYON_NTT_SHOUP: 0 = Montgomery everywhere, 1 = Shoup everywhere)
-    const bool shoup = kShoup && (shoup_mode_ == 1 || (shoup_mode_ == 2 && p > 0));
-    // (A/B, TACHYON_NTT_VARIANT: bit 0 = the Montgomery radix-4 pass at >= 5
-    // waves/SIMD, bit 1 = the Shoup radix-4 passes without the twiddle
-    // prefetch at >= 5 waves/SIMD)
-#ifdef TACHYON_TUNING_KNOBS
-    // tiles above 64 KiB (TACHYON_NTT_LDS_ELEMS > 2048) need the kernel's dynamic-LDS limit raised
-    auto allow = [&](const void* k) {
-      if (lds > 64 * 1024) TA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    };
-    if (shoup) {
-      auto kern = radix_ == 1 ? dif_pass_kernel<Fr, Tw, 1> : radix_ == 2 ? dif_pass_kernel<Fr, Tw, 2>
-                                                                         : dif_pass_kernel<Fr, Tw, 3>;
-      if (radix_ == 2 && (ntt_variant_ & 2)) kern = dif_pass_kernel<Fr, Tw, 2, false, 5>;
-      allow(reinterpret_cast<const void*>(kern));
-      hipLaunchKernelGGL(kern, dim3(blocks, gy), dim3(kBlock), lds, stream_, src, dst, tw, a);
-    } else {
-      auto kern = radix_ == 1 ? dif_pass_kernel<Fr, Fr, 1> : radix_ == 2 ? dif_pass_kernel<Fr, Fr, 2>
-                                                                         : dif_pass_kernel<Fr, Fr, 3>;
-      if (radix_ == 2 && (ntt_variant_ & 1)) kern = dif_pass_kernel<Fr, Fr, 2, true, 5>;
-      allow(reinterpret_cast<const void*>(kern));
-      hipLaunchKernelGGL(kern, dim3(blocks, gy), dim3(kBlock), lds, stream_, src, dst, twm, a);
-    }
-#else
-    // release schedule: radix-4 register steps (2 DIF stages per LDS round trip)
-    if (lds > 64 * 1024) throw std::runtime_error("tachyon_mi355x: NTT pass tile above 64 KiB in a release build");
-    if (shoup)
-      hipLaunchKernelGGL((dif_pass_kernel<Fr, Tw, 2>), dim3(blocks, gy), dim3(kBlock), lds, stream_, src,
-                         dst, tw, a);
-    else
-      hipLaunchKernelGGL((dif_pass_kernel<Fr, Fr, 2>), dim3(blocks, gy), dim3(kBlock), lds, stream_, src,
-                         dst, twm, a);
-#endif
-    TA_HIP(hipGetLastError());
-    if (profile_) TA_HIP(hipEventRecord(ev_[p + 1], stream_));
+  if (std::is_same_v<Fr, Bn254Fr> && (variant_ & 1)) {
+    run29(d_data, inverse, batch, src_in, fs);
+  } else {
+    const StageTables st = stage_tables(inverse);
+    const Tables32<Fr> tables{static_cast<const typename Tables32<Fr>::Tw*>(st.tw), st.twm, shoup_mode_, radix_,
+                              ntt_variant_};
+    void* scratch = plan_.size() > 1 ? scratch_.ensure(batch * n_ * sizeof(Fr)) : nullptr;
+    const CosetPtrs<Fr> cp{coset_lo_.as<Fr>(), coset_hi_.as<Fr>(), icoset_lo_.as<Fr>(), icoset_hi_.as<Fr>()};
+    run_passes(tables, plan_, log_n_, inverse, batch, pack_log(batch), size_inv_, has_offset_ ? &cp : nullptr, fs, src_in,
+               d_data, scratch, stream_, profile_ ? ev_.data() : nullptr);
   }
   if (profile_) {
     TA_HIP(hipEventSynchronize(ev_[plan_.size()]));
@@ -1023,81 +507,17 @@ void NttDomain<Fr>::run(Fr* d_data, bool inverse, size_t batch, const Fr* src_in
   }
 }
 
-
-// BN254 Fr: the passes over 9 x 29-bit limbs (dif29_pass_kernel); the same
-// pass plan, modes and scratch discipline as run()
+// BN254 Fr: the passes over 9 x 29-bit limbs (dif29_pass_kernel), called by run()
 template <class Fr>
 void NttDomain<Fr>::run29(Fr* d_data, bool inverse, size_t batch, const Fr* src_in, const FourStepTw<Fr>* fs) {
   if constexpr (std::is_same_v<Fr, Bn254Fr>) {
-    const auto* tm = (inverse ? t29m_inv_ : t29m_fwd_).template as<fr29::TwMont29>();
-    const auto* ts = (inverse ? t29s_inv_ : t29s_fwd_).template as<fr29::TwShoup29>();
-    F29* scratch = plan_.size() > 1 ? static_cast<F29*>(scratch29_.ensure(batch * n_ * sizeof(F29))) : nullptr;
-    if (profile_) TA_HIP(hipEventRecord(ev_[0], stream_));
-    for (size_t p = 0; p < plan_.size(); ++p) {
-      const Pass& ps = plan_[p];
-      PassArgs<Fr> a{};
-      a.L = log_n_;
-      a.s0 = ps.s0;
-      a.k = ps.k;
-      a.log_m = ps.log_m;
-      a.final_pass = ps.final_pass ? 1u : 0u;
-      a.pow_bits = pow_bits_;
-      a.mode = 0;
-      if (p == 0 && !inverse && has_offset_) {
-        a.mode |= kLoadCoset;
-        a.load_lo = coset_lo_.as<Fr>();
-        a.load_hi = coset_hi_.as<Fr>();
-      }
-      if (ps.final_pass && inverse) {
-        if (has_offset_) {
-          a.mode |= kStoreCoset;
-          a.store_lo = icoset_lo_.as<Fr>();
-          a.store_hi = icoset_hi_.as<Fr>();
-        } else {
-          a.mode |= kStoreScale;
-          a.scale = size_inv_;
-        }
-      }
-      if (fs) {
-        a.fs = *fs;
-        if (fs->rows) {
-          if (p == 0 && !inverse) a.mode |= kLoadXch;
-          if (ps.final_pass && inverse) a.mode |= kStoreXch;
-        } else {
-          if (p == 0 && inverse) a.mode |= kLoadTw4;
-          if (ps.final_pass && !inverse) a.mode |= kStoreTw4;
-        }
-      }
-      // first pass: data / src_in (32 B) -> scratch (36 B); middle: scratch in place; last: scratch -> data
-      const void* src = (p == 0) ? static_cast<const void*>(src_in ? src_in : d_data) : scratch;
-      void* dst = ps.final_pass ? static_cast<void*>(d_data) : scratch;
-      a.pack = pack_log(batch);  // a one-pass transform smaller than a tile: several entries per workgroup
-      if (a.pack) a.log_m = a.pack;
-      const uint32_t elems = (1u << a.log_m) << ps.k;
-      const uint32_t blocks = a.pack ? 1u : (uint32_t)(n_ / elems);
-      const uint32_t gy = (uint32_t)(batch >> a.pack);
-      // the 29-bit kernel's LDS planes are sized for kMaxLdsElems (tuning plans with larger tiles: 32-bit only)
-      if (elems > kMaxLdsElems) throw std::runtime_error("tachyon_mi355x: 29-bit NTT pass tile above its LDS planes");
-      const bool swz = (variant_ & 2) != 0;
-      if (p == 0) {
-        auto* k0 = swz ? &dif29_pass_kernel<true, true, fr29::TwMont29> : &dif29_pass_kernel<true, false, fr29::TwMont29>;
-        hipLaunchKernelGGL(k0, dim3(blocks, gy), dim3(kBlock), 0, stream_, src, dst,
-                           Tw29Table<fr29::TwMont29>{tm, 0u}, a);
-      } else {
-        auto* k1 = swz ? &dif29_pass_kernel<false, true, fr29::TwShoup29>
-                       : &dif29_pass_kernel<false, false, fr29::TwShoup29>;
-        hipLaunchKernelGGL(k1, dim3(blocks, gy), dim3(kBlock), 0, stream_, src, dst,
-                           Tw29Table<fr29::TwShoup29>{ts, (uint32_t)split29_}, a);
-      }
-      TA_HIP(hipGetLastError());
-      if (profile_) TA_HIP(hipEventRecord(ev_[p + 1], stream_));
-    }
-    if (profile_) {
-      TA_HIP(hipEventSynchronize(ev_[plan_.size()]));
-      timings_.passes.assign(plan_.size(), 0.f);
-      for (size_t p = 0; p < plan_.size(); ++p) TA_HIP(hipEventElapsedTime(&timings_.passes[p], ev_[p], ev_[p + 1]));
-      TA_HIP(hipEventElapsedTime(&timings_.total, ev_[0], ev_[plan_.size()]));
-    }
+    const Tables29<Fr> tables{(inverse ? t29m_inv_ : t29m_fwd_).template as<fr29::TwMont29>(),
+                              (inverse ? t29s_inv_ : t29s_fwd_).template as<fr29::TwShoup29>(), (uint32_t)split29_,
+                              (variant_ & 2) != 0};
+    void* scratch = plan_.size() > 1 ? scratch29_.ensure(batch * n_ * sizeof(F29)) : nullptr;
+    const CosetPtrs<Fr> cp{coset_lo_.as<Fr>(), coset_hi_.as<Fr>(), icoset_lo_.as<Fr>(), icoset_hi_.as<Fr>()};
+    run_passes(tables, plan_, log_n_, inverse, batch, pack_log(batch), size_inv_, has_offset_ ? &cp : nullptr, fs, src_in,
+               d_data, scratch, stream_, profile_ ? ev_.data() : nullptr);
   }
 }
 
@@ -1136,50 +556,6 @@ void NttDomain<Fr>::inverse_host(const Fr* in, size_t len, Fr* out) {
 
 // ---------------------------------------------------------------------------
 // NttGenDomain: one generator, every power-of-two size up to its order
-
-namespace {
-
-template <class Fr>
-struct CosetPtrs {
-  const Fr* lo;
-  const Fr* hi;
-  const Fr* ilo;
-  const Fr* ihi;
-};
-
-// PassArgs of pass `ps` of a 2^L-point transform, as NttDomain<Fr>(2^L)::run
-// fills them (no four-step modes): c = the coset's power tables, null = plain
-template <class Fr, class Pass>
-PassArgs<Fr> sub_pass_args(const Pass& ps, uint32_t L, bool first, bool inverse, const Fr& size_inv,
-                           const CosetPtrs<Fr>* c, uint32_t pack) {
-  PassArgs<Fr> a{};
-  a.L = L;
-  a.s0 = ps.s0;
-  a.k = ps.k;
-  a.log_m = pack ? pack : ps.log_m;
-  a.final_pass = ps.final_pass ? 1u : 0u;
-  a.pow_bits = (L + 1) / 2;
-  a.mode = 0;
-  if (first && !inverse && c) {
-    a.mode |= kLoadCoset;
-    a.load_lo = c->lo;
-    a.load_hi = c->hi;
-  }
-  if (ps.final_pass && inverse) {
-    if (c) {
-      a.mode |= kStoreCoset;
-      a.store_lo = c->ilo;
-      a.store_hi = c->ihi;
-    } else {
-      a.mode |= kStoreScale;
-      a.scale = size_inv;
-    }
-  }
-  a.pack = pack;
-  return a;
-}
-
-}  // namespace
 
 template <class Fr>
 NttGenDomain<Fr>::NttGenDomain(hipStream_t stream) : stream_(stream) {
@@ -1223,7 +599,7 @@ bool NttGenDomain<Fr>::init(const Fr& group_gen) {
     cap29s_ = std::min<size_t>(n, size_t(1) << 14);
     DeviceBuffer* bm[2] = {&t29m_fwd_, &t29m_inv_};
     DeviceBuffer* bs[2] = {&t29s_fwd_, &t29s_inv_};
-    const Fr* mont[2] = {base_->twm_fwd_.template as<Fr>(), base_->twm_inv_.template as<Fr>()};
+    const Fr* mont[2] = {base_->stage_tables(false).twm, base_->stage_tables(true).twm};
     for (int dir = 0; dir < 2 && n > 1; ++dir) {
       const uint32_t cm = (uint32_t)(cap29m_ - 1), cs = (uint32_t)(cap29s_ - 1);
       auto* m29 = static_cast<fr29::TwMont29*>(bm[dir]->ensure(cm * sizeof(fr29::TwMont29)));
@@ -1257,8 +633,7 @@ void NttGenDomain<Fr>::release() {
 template <class Fr>
 size_t NttGenDomain<Fr>::table_bytes() const {
   if (!base_) return 0;
-  size_t bytes = base_->tw_fwd_.capacity() + base_->tw_inv_.capacity() + base_->twm_fwd_.capacity() +
-                 base_->twm_inv_.capacity() + t29m_fwd_.capacity() + t29m_inv_.capacity() + t29s_fwd_.capacity() +
+  size_t bytes = base_->stage_table_bytes() + t29m_fwd_.capacity() + t29m_inv_.capacity() + t29s_fwd_.capacity() +
                  t29s_inv_.capacity();
   for (const CosetTables& c : cosets_) bytes += c.lo.capacity() + c.hi.capacity() + c.ilo.capacity() + c.ihi.capacity();
   return bytes;
@@ -1305,15 +680,6 @@ bool NttGenDomain<Fr>::uses29(uint32_t log_m) const {
   return std::is_same_v<Fr, Bn254Fr> && log_m >= 1 && log_m <= 20;
 }
 
-// NttDomain::pack_log of a 2^log_m-point domain
-template <class Fr>
-uint32_t NttGenDomain<Fr>::pack_log(uint32_t log_m, size_t batch) const {
-  if (plans_[log_m].size() != 1 || batch < 2) return 0;
-  uint32_t p = 0;
-  while (batch % (size_t(2) << p) == 0 && ((size_t(1) << log_m) << (p + 1)) <= kMaxLdsElems) ++p;
-  return p;
-}
-
 template <class Fr>
 void NttGenDomain<Fr>::run(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const Fr& coset) {
   if (!base_) throw std::runtime_error("tachyon_mi355x: NTT run before init");
@@ -1336,72 +702,38 @@ void NttGenDomain<Fr>::run_host(Fr* data, uint32_t log_m, bool inverse, size_t b
   TA_HIP(hipStreamSynchronize(stream_));
 }
 
-// The 32-bit passes of NttDomain::run on the size-N tables' suffix: the table
-// base advanced by N - m, PassArgs::L = log_m
+// The 32-bit passes on the size-N tables' suffix: the table bases advanced by
+// N - m, PassArgs::L = log_m
 template <class Fr>
 void NttGenDomain<Fr>::run32(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const CosetTables* ct) {
-  using Tw = typename NttTw<Fr>::type;
-  constexpr bool kShoup = !std::is_same_v<Tw, Fr>;
   const size_t m = size_t(1) << log_m, shift = (size_t(1) << log_n_) - m;
-  const Tw* tw = (inverse ? base_->tw_inv_ : base_->tw_fwd_).template as<Tw>() + shift;
-  const Fr* twm = kShoup ? (inverse ? base_->twm_inv_ : base_->twm_fwd_).template as<Fr>() + shift
-                         : reinterpret_cast<const Fr*>(tw);
+  const auto st = base_->stage_tables(inverse);
+  const Tables32<Fr> tables{static_cast<const typename Tables32<Fr>::Tw*>(st.tw) + shift, st.twm + shift};
   const std::vector<Pass>& plan = plans_[log_m];
-  Fr* scratch = plan.size() > 1 ? static_cast<Fr*>(scratch_.ensure(batch * m * sizeof(Fr))) : d_data;
+  void* scratch = plan.size() > 1 ? scratch_.ensure(batch * m * sizeof(Fr)) : nullptr;
   CosetPtrs<Fr> cp{};
   if (ct) cp = {ct->lo.template as<Fr>(), ct->hi.template as<Fr>(), ct->ilo.template as<Fr>(), ct->ihi.template as<Fr>()};
-  const uint32_t pack = pack_log(log_m, batch);
-  for (size_t p = 0; p < plan.size(); ++p) {
-    const Pass& ps = plan[p];
-    const PassArgs<Fr> a = sub_pass_args<Fr>(ps, log_m, p == 0, inverse, size_inv_[log_m], ct ? &cp : nullptr, pack);
-    const Fr* src = (p == 0) ? d_data : scratch;
-    Fr* dst = ps.final_pass ? d_data : scratch;
-    const uint32_t elems = (1u << a.log_m) << ps.k;
-    const uint32_t blocks = pack ? 1u : (uint32_t)(m / elems);
-    const uint32_t gy = (uint32_t)(batch >> pack);
-    const size_t lds = (size_t)elems * sizeof(Fr);
-    // Montgomery twiddles in the first pass, Shoup entries in the later ones (NttDomain::run)
-    if (kShoup && p > 0)
-      hipLaunchKernelGGL((dif_pass_kernel<Fr, Tw, 2>), dim3(blocks, gy), dim3(kBlock), lds, stream_, src, dst, tw, a);
-    else
-      hipLaunchKernelGGL((dif_pass_kernel<Fr, Fr, 2>), dim3(blocks, gy), dim3(kBlock), lds, stream_, src, dst, twm, a);
-    TA_HIP(hipGetLastError());
-  }
+  run_passes<Fr>(tables, plan, log_m, inverse, batch, pack_log(plan.size(), log_m, batch), size_inv_[log_m],
+                 ct ? &cp : nullptr, nullptr, nullptr, d_data, scratch, stream_, nullptr);
 }
 
-// The 29-bit passes of NttDomain::run29 (BN254 Fr, log_m <= 20) on the bounded
-// 29-bit tables: entry (stage s, index j) of the size-m network is entry
-// (m - (m >> s)) + j + (cap - m) of a table holding the last cap - 1 entries
+// The 29-bit passes (BN254 Fr, log_m <= 20) on the bounded 29-bit tables:
+// entry (stage s, index j) of the size-m network is entry (m - (m >> s)) + j +
+// (cap - m) of a table holding the last cap - 1 entries
 template <class Fr>
 void NttGenDomain<Fr>::run29(Fr* d_data, uint32_t log_m, bool inverse, size_t batch, const CosetTables* ct) {
   if constexpr (std::is_same_v<Fr, Bn254Fr>) {
     const size_t m = size_t(1) << log_m;
-    const auto* tm = (inverse ? t29m_inv_ : t29m_fwd_).template as<fr29::TwMont29>() + (cap29m_ - m);
-    const auto* ts = (inverse ? t29s_inv_ : t29s_fwd_).template as<fr29::TwShoup29>();
-    uint32_t ts_off = 0;
-    if (m <= cap29s_) ts += cap29s_ - m;
-    else ts_off = (uint32_t)(m - cap29s_);  // (later passes read stages >= k0 only: m >> k0 <= 2^14)
+    Tables29<Fr> tables{(inverse ? t29m_inv_ : t29m_fwd_).template as<fr29::TwMont29>() + (cap29m_ - m),
+                        (inverse ? t29s_inv_ : t29s_fwd_).template as<fr29::TwShoup29>(), 0u, false};
+    if (m <= cap29s_) tables.ts += cap29s_ - m;
+    else tables.ts_off = (uint32_t)(m - cap29s_);  // (later passes read stages >= k0 only: m >> k0 <= 2^14)
     const std::vector<Pass>& plan = plans_[log_m];
-    F29* scratch = plan.size() > 1 ? static_cast<F29*>(scratch_.ensure(batch * m * sizeof(F29))) : nullptr;
+    void* scratch = plan.size() > 1 ? scratch_.ensure(batch * m * sizeof(F29)) : nullptr;
     CosetPtrs<Fr> cp{};
     if (ct) cp = {ct->lo.template as<Fr>(), ct->hi.template as<Fr>(), ct->ilo.template as<Fr>(), ct->ihi.template as<Fr>()};
-    const uint32_t pack = pack_log(log_m, batch);
-    for (size_t p = 0; p < plan.size(); ++p) {
-      const Pass& ps = plan[p];
-      const PassArgs<Fr> a = sub_pass_args<Fr>(ps, log_m, p == 0, inverse, size_inv_[log_m], ct ? &cp : nullptr, pack);
-      const void* src = (p == 0) ? static_cast<const void*>(d_data) : scratch;
-      void* dst = ps.final_pass ? static_cast<void*>(d_data) : scratch;
-      const uint32_t elems = (1u << a.log_m) << ps.k;
-      const uint32_t blocks = pack ? 1u : (uint32_t)(m / elems);
-      const uint32_t gy = (uint32_t)(batch >> pack);
-      if (p == 0)
-        hipLaunchKernelGGL((dif29_pass_kernel<true, false, fr29::TwMont29>), dim3(blocks, gy), dim3(kBlock), 0, stream_,
-                           src, dst, Tw29Table<fr29::TwMont29>{tm, 0u}, a);
-      else
-        hipLaunchKernelGGL((dif29_pass_kernel<false, false, fr29::TwShoup29>), dim3(blocks, gy), dim3(kBlock), 0,
-                           stream_, src, dst, Tw29Table<fr29::TwShoup29>{ts, ts_off}, a);
-      TA_HIP(hipGetLastError());
-    }
+    run_passes<Fr>(tables, plan, log_m, inverse, batch, pack_log(plan.size(), log_m, batch), size_inv_[log_m],
+                   ct ? &cp : nullptr, nullptr, nullptr, d_data, scratch, stream_, nullptr);
   }
 }
 

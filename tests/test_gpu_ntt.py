@@ -255,6 +255,34 @@ def test_field29_extreme_inputs():
             d.close()
 
 
+def test_profile_pass_timings():
+    """set_profile / last_timings (tools/ntt_probe.py, tools/tune_ntt.py): with
+    the per-pass events on, transforms of 2^7 (one pass), 2^12 (two) and 2^17
+    (three) elements on the 32-bit (variant 0) and 29-bit (1) passes still equal
+    the oracle bytewise and report ceil(log_n / 8) positive pass times, none
+    above the total (the events are nested, so only the rounding of the
+    millisecond floats is allowed for: one microsecond); a transform after
+    profiling is turned off again is unchanged."""
+    for logn in (7, 12, 17):
+        n = 1 << logn
+        coeffs = O.gen_scalars("bn254_fr", 4000 + logn, n).tobytes()
+        evals = O.fft(coeffs, n)
+        back = O.ifft(evals, n)
+        for variant in (0, 1):
+            d = domain(n)
+            d.set_variant(variant)
+            d.set_profile(True)
+            for run, data, want in ((d.fft, coeffs, evals), (d.ifft, evals, back)):
+                assert run(data) == want, (logn, variant)
+                total, passes = d.last_timings()
+                assert len(passes) == (logn + 7) // 8, (logn, variant, passes)
+                assert all(p > 0 for p in passes), (logn, variant, passes)
+                assert total >= max(passes) - 1e-3, (logn, variant, total, passes)
+            d.set_profile(False)
+            assert d.fft(coeffs) == evals, (logn, variant)
+            d.close()
+
+
 @pytest.mark.parametrize("log_n,devices", [(4, [0, 0]), (10, [0, 0]), (13, [0, 0, 0, 0]), (16, [0] * 8),
                                            (20, [0, 0]), (11, [0, 0, 0]), (20, [0, 0, 0, 0]), (9, [0] * 5)])
 def test_multi_device_domain_logical(log_n, devices):
