@@ -15,22 +15,11 @@
 
 #include "../dist/comm.h"
 #include "../groth16/groth16.h"
+#include "capi_guard.h"
 
 using namespace tachyon_amd;
 
 namespace {
-
-[[noreturn]] void die(const char* fn, const char* what) {
-  fprintf(stderr, "[tachyon_mi355x] %s failed: %s\n", fn, what);
-  fflush(stderr);
-  abort();
-}
-
-#define GUARD_BEGIN try {
-#define GUARD_END                                                \
-  }                                                              \
-  catch (const std::exception& e) { die(__func__, e.what()); }   \
-  catch (...) { die(__func__, "unknown exception"); }
 
 using BnProver = groth16::Groth16Prover<Bn254G1, Bn254G2>;
 using BlsProver = groth16::Groth16Prover<Bls381G1, Bls381G2>;

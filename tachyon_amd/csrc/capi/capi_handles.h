@@ -1,27 +1,13 @@
 // The opaque handles of the BabyBear entry points that more than one capi_*.hip
-// file takes (include/tachyon_mi355x.h declares them), and the guard their
-// entry points run under.
+// file takes (include/tachyon_mi355x.h declares them); their entry points run
+// under guarded() (capi_guard.h).
 #pragma once
 #include <memory>
 
 #include "../fri/challenger_bb.h"
 #include "../fri/fri_bb.h"
 #include "../hash/merkle_bb.h"
-
-namespace tachyon_amd {
-
-// What `body` returns, or `fallback` if it throws: nothing aborts across the
-// C-ABI.  A bool becomes the entry point's 1 or 0.
-template <class T, class Fn>
-T guarded(T fallback, Fn&& body) {
-  try {
-    return body();
-  } catch (...) {
-    return fallback;
-  }
-}
-
-}  // namespace tachyon_amd
+#include "capi_guard.h"
 
 struct tachyon_mi355x_baby_bear_merkle_tree {
   std::unique_ptr<tachyon_amd::hash::BbMerkleTree> tree;

@@ -8,30 +8,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <memory>
 #include <vector>
 
 #include "../kzg/kzg.h"
+#include "capi_guard.h"
 #include "kzg_open_validate.h"
 
 using namespace tachyon_amd;
-
-namespace {
-
-[[noreturn]] void die(const char* fn, const char* what) {
-  fprintf(stderr, "[tachyon_mi355x] %s failed: %s\n", fn, what);
-  fflush(stderr);
-  abort();
-}
-
-#define GUARD_BEGIN try {
-#define GUARD_END                                                \
-  }                                                              \
-  catch (const std::exception& e) { die(__func__, e.what()); }   \
-  catch (...) { die(__func__, "unknown exception"); }
-
-}  // namespace
 
 struct tachyon_mi355x_kzg {
   int curve;  // 0 bn254_g1, 2 bls12_381_g1

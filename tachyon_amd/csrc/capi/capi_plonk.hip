@@ -5,13 +5,12 @@
 // after that returns 0 with a message: this entry point never aborts.
 #include "../../../include/tachyon_mi355x.h"
 
-#include <cstdio>
 #include <cstring>
-#include <exception>
 #include <mutex>
 #include <vector>
 
 #include "../plonk/grand_product.h"
+#include "capi_guard.h"
 #include "grand_product_validate.h"
 
 using namespace tachyon_amd;
@@ -76,19 +75,13 @@ int tachyon_mi355x_grand_product_chains(int field, size_t n, size_t usable_rows,
   if (!gp_validate::check(field, n, usable_rows, omega, delta, polys, chain_lens, num_chains, blinds, out_z,
                           plonk::kGpTile, plonk::kGpMaxTiles))
     return 0;
-  try {
+  return guarded_report(__func__, 0, [&] {
     if (field == 0)
       run_chains<Bn254Fr>(n, usable_rows, omega, delta, polys, chain_lens, num_chains, blinds, out_z, out_last);
     else
       run_chains<Bls381Fr>(n, usable_rows, omega, delta, polys, chain_lens, num_chains, blinds, out_z, out_last);
     return 1;
-  } catch (const std::exception& e) {
-    fprintf(stderr, "[tachyon_mi355x] %s failed: %s\n", __func__, e.what());
-  } catch (...) {
-    fprintf(stderr, "[tachyon_mi355x] %s failed: unknown exception\n", __func__);
-  }
-  fflush(stderr);
-  return 0;
+  });
 }
 
 size_t tachyon_mi355x_grand_product_tile_rows(void) { return plonk::kGpTile; }

@@ -54,7 +54,7 @@ def test_partition_tiles_every_point_window_pair_once(curve, world, split):
 
 def test_auto_follows_the_plan_table():
     plans = bench.hybrid_plans()
-    # the measured table in capi.hip (kHybridPlans)
+    # the measured table in capi_msm.hip (kHybridPlans)
     assert plans == {("bn254_g1", 8): (2, 19), ("bls12_381_g2", 4): (2, 19), ("bls12_381_g2", 8): (4, 16)}
     for (curve, world), (q, c) in plans.items():
         split, _, n, wrange, cc, p, qq, _ = bench.msm_partition(_args("auto"), curve, world, 0, 1 << 20)
