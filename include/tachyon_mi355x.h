@@ -913,10 +913,28 @@ TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_run_points(int curve, void* ctx, con
                                                       int base_form, const void* scalars, size_t scalars_size,
                                                       int form, void* out);
 TACHYON_C_EXPORT void tachyon_mi355x_msm_gpu_set_window_bits(int curve, void* ctx, unsigned c);
+/* `windows` windows of two widths for the later plain runs of the context: with
+ * c_lo = floor((bits + 1) / windows), the top bits + 1 - windows c_lo windows are
+ * c_lo + 1 bits wide and the rest c_lo, bits + 1 in all (the signed digits of a
+ * bits-bit scalar); sort keys are bucket indices.  0 = off (the size's default
+ * plan).  Only a plain run takes them: a batch, a fold or forced window bits
+ * are refused while they are set (those entry points return 0), and a window
+ * range aborts.  Returns 1, or 0 (nothing changed) for a layout whose widths
+ * leave 2 .. 26 bits or whose bucket indices need more than 24 key bits, and
+ * with window bits forced. */
+TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_set_mixed_windows(int curve, void* ctx, unsigned windows);
+/* The layout of `windows` mixed-width windows for the curve's scalar field (no
+ * GPU needed): c_lo, the number of wide windows (the top ones), the sort-key
+ * bits, and windows + 1 bit offsets and bucket offsets (the last = the totals).
+ * Any output may be NULL.  Returns 0 where set_mixed_windows refuses. */
+TACHYON_C_EXPORT int tachyon_mi355x_msm_mixed_layout(int curve, unsigned windows, unsigned* c_lo, unsigned* n_wide,
+                                                     unsigned* key_bits, unsigned* bit_offsets,
+                                                     unsigned* bucket_offsets);
 TACHYON_C_EXPORT void tachyon_mi355x_msm_gpu_set_profile(int curve, void* ctx, int on);
 /* kernel-variant bits for A/B tuning in one process (0 = default schedule).
  * Every accepted variant computes the same MSM; returns 0 (nothing changed)
- * for bits outside 0x3FFFFBF (bits 0-25 but 6; bit 23: two-level window sums
+ * for bits outside 0x3FFFFBF | 1 << 27 (bits 0-25 but 6; bit 27: the uniform
+ * window plan where mixed widths are the size's default; bit 23: two-level window sums
  * for the G2 / BLS12-381 G1 / FIPS reductions, measured slower; bit 24: the
  * G2 window segment sums in two passes; bit 25: the limb-field G1
  * accumulations read their entries by 8-byte loads, not LDS-staged chunks). */
@@ -947,7 +965,8 @@ TACHYON_C_EXPORT size_t tachyon_mi355x_msm_gpu_held_bytes(int curve, const void*
  * bit 4 the lane-pair G2 accumulation, bit 5 over the 28-bit-limb field
  * (BLS12-381 G1 / G2), bit 6 the chain-flag debug check ran, bit 7 the
  * limb-field accumulation read its sorted entries through LDS (64-byte chunks
- * by LDS-DMA; BN254 / BLS12-381 G1, BLS12-381 G2). */
+ * by LDS-DMA; BN254 / BLS12-381 G1, BLS12-381 G2), bit 8 windows of two
+ * widths (set_mixed_windows, or the default of BN254 G1 from 2^26 points). */
 TACHYON_C_EXPORT unsigned tachyon_mi355x_msm_gpu_last_schedule(int curve, const void* ctx);
 /* Diagnostic: mixed additions per second (G/s) of the curve's bucket
  * accumulation field code in registers on the current device (no gathers, no
@@ -976,7 +995,8 @@ TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_set_devices(int curve, void* ctx, co
  * shards (0 for a single-device context).  Any output pointer may be NULL. */
 TACHYON_C_EXPORT size_t tachyon_mi355x_msm_gpu_last_shards(int curve, const void* ctx, float* shard_ms,
                                                            size_t* shard_points, int* shard_devices, size_t cap);
-/* window bits / windows the planner picks for `size` points */
+/* window bits / windows the planner picks for a plain run of `size` points
+ * (mixed widths: the narrow windows' bits) */
 TACHYON_C_EXPORT void tachyon_mi355x_msm_plan(int curve, size_t size, unsigned* c, unsigned* windows);
 /* Host-side group arithmetic on affine points (multi-GPU partial sums):
  * out = sum of `count` affine points. */

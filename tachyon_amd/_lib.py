@@ -149,6 +149,8 @@ SIGNATURES = [
     ("tachyon_mi355x_msm_gpu_window_range_affine", None, [i32, vp, vp, vp, sz, ctypes.c_uint, ctypes.c_uint, vp]),
     ("tachyon_mi355x_msm_gpu_batch_affine", i32, [i32, vp, vp, sz, vp, sz, vp]),
     ("tachyon_mi355x_msm_gpu_plan_windows", ctypes.c_uint, [i32, vp, sz]),
+    ("tachyon_mi355x_msm_gpu_set_mixed_windows", i32, [i32, vp, ctypes.c_uint]),
+    ("tachyon_mi355x_msm_mixed_layout", i32, [i32, ctypes.c_uint] + [vp] * 5),
     ("tachyon_mi355x_msm_gpu_fold_bases", i32, [i32, vp, vp, sz, ctypes.c_uint, vp]),
     ("tachyon_mi355x_msm_gpu_folded_affine", i32, [i32, vp, vp, vp, sz, ctypes.c_uint, vp]),
     ("tachyon_mi355x_msm_gpu_create", vp, [i32, vp]),

@@ -453,6 +453,15 @@ tachyon_bls12_381_g2_jacobian* tachyon_bls12_381_g2_affine_msm_gpu(tachyon_bls12
 }
 
 // ---- curve-generic extensions ----
+// W of the uniform plan -- what a fold divides -- or 0 while mixed-width
+// windows are set (a batch, a fold or a window range with them is refused)
+static unsigned uniform_windows(int curve, const void* ctx, size_t size) {
+  GUARD_BEGIN CURVE_DISPATCH(curve, {
+    const auto& m = static_cast<const MsmCtx<C>*>(ctx)->impl;
+    return m.mixed_windows() ? 0u : m.fold_windows(size);
+  }) GUARD_END
+  return 0;
+}
 void tachyon_mi355x_msm_gpu_affine(int curve, void* ctx, const void* bases, const void* scalars, size_t size,
                                    void* out_affine) {
   GUARD_BEGIN CURVE_DISPATCH(curve, msm_affine_out<C>(ctx, bases, scalars, size, out_affine)) GUARD_END
@@ -464,7 +473,7 @@ void tachyon_mi355x_msm_gpu_window_range_affine(int curve, void* ctx, const void
 }
 int tachyon_mi355x_msm_gpu_batch_affine(int curve, void* ctx, const void* bases, size_t len, const void* scalars,
                                         size_t count, void* out_affine) {
-  if (!is_device_pointer(bases)) return 0;
+  if (!is_device_pointer(bases) || (count > 1 && uniform_windows(curve, ctx, len) == 0)) return 0;
   GUARD_BEGIN CURVE_DISPATCH(curve, msm_batch_out<C>(ctx, bases, len, scalars, count, out_affine)) GUARD_END
   return 1;
 }
@@ -475,7 +484,8 @@ unsigned tachyon_mi355x_msm_gpu_plan_windows(int curve, const void* ctx, size_t 
 int tachyon_mi355x_msm_gpu_fold_bases(int curve, void* ctx, const void* bases, size_t size, unsigned fold,
                                       void* out_bases) {
   if (fold == 0 || !is_device_pointer(bases) || !is_device_pointer(out_bases)) return 0;
-  if (tachyon_mi355x_msm_gpu_plan_windows(curve, ctx, size) % fold != 0) return 0;  // refused, nothing written
+  const unsigned W = uniform_windows(curve, ctx, size);
+  if (W == 0 || W % fold != 0) return 0;  // refused, nothing written
   GUARD_BEGIN CURVE_DISPATCH(curve, static_cast<MsmCtx<C>*>(ctx)->impl.fold_bases(bases, size, fold, out_bases))
   GUARD_END
   return 1;
@@ -483,7 +493,8 @@ int tachyon_mi355x_msm_gpu_fold_bases(int curve, void* ctx, const void* bases, s
 int tachyon_mi355x_msm_gpu_folded_affine(int curve, void* ctx, const void* folded_bases, const void* scalars,
                                          size_t size, unsigned fold, void* out_affine) {
   if (fold == 0 || !is_device_pointer(folded_bases) || !is_device_pointer(scalars)) return 0;
-  if (fold > 1 && tachyon_mi355x_msm_gpu_plan_windows(curve, ctx, size) % fold != 0) return 0;
+  const unsigned W = uniform_windows(curve, ctx, size);
+  if (W == 0 || (fold > 1 && W % fold != 0)) return 0;
   GUARD_BEGIN CURVE_DISPATCH(curve, msm_folded_out<C>(ctx, folded_bases, scalars, size, fold, out_affine)) GUARD_END
   return 1;
 }
@@ -560,6 +571,36 @@ void tachyon_mi355x_msm_gpu_set_window_bits(int curve, void* ctx, unsigned c) {
   GUARD_BEGIN
   CURVE_DISPATCH(curve, static_cast<MsmCtx<C>*>(ctx)->set([&](auto& m) { m.set_force_window_bits(c); }))
   GUARD_END
+}
+int tachyon_mi355x_msm_gpu_set_mixed_windows(int curve, void* ctx, unsigned windows) {
+  if (!ctx || curve < 0 || curve > 3) return 0;
+  const unsigned bits = curve < 2 ? Bn254Fr::Config::kModulusBits : Bls381Fr::Config::kModulusBits;
+  if (windows && !msm::MsmPlan::mixed_layout_ok(bits, windows)) return 0;  // refused, nothing changed
+  GUARD_BEGIN
+  CURVE_DISPATCH(curve, {
+    auto* m = static_cast<MsmCtx<C>*>(ctx);
+    if (windows && m->impl.force_window_bits()) return 0;  // not with forced window bits
+    m->set([&](auto& g) { g.set_mixed_windows(windows); });
+  })
+  GUARD_END
+  return 1;
+}
+int tachyon_mi355x_msm_mixed_layout(int curve, unsigned windows, unsigned* c_lo, unsigned* n_wide, unsigned* key_bits,
+                                    unsigned* bit_offsets, unsigned* bucket_offsets) {
+  if (curve < 0 || curve > 3) return 0;
+  const unsigned bits = curve < 2 ? Bn254Fr::Config::kModulusBits : Bls381Fr::Config::kModulusBits;
+  if (!msm::MsmPlan::mixed_layout_ok(bits, windows)) return 0;
+  GUARD_BEGIN
+  const msm::MsmPlan p = msm::MsmPlan::make_mixed(1, bits, windows);
+  if (c_lo) *c_lo = p.c;
+  if (n_wide) *n_wide = p.n_wide;
+  if (key_bits) *key_bits = msm::kMixedKeyBits;
+  for (unsigned w = 0; w <= windows; ++w) {
+    if (bit_offsets) bit_offsets[w] = p.bit_offset(w);
+    if (bucket_offsets) bucket_offsets[w] = (unsigned)p.bucket_offset(w);
+  }
+  GUARD_END
+  return 1;
 }
 int tachyon_mi355x_msm_gpu_set_devices(int curve, void* ctx, const int* device_ids, size_t count) {
   int n = 0;
@@ -642,7 +683,7 @@ size_t tachyon_mi355x_msm_gpu_held_bytes(int curve, const void* ctx) {
 }
 void tachyon_mi355x_msm_plan(int curve, size_t size, unsigned* c, unsigned* windows) {
   GUARD_BEGIN CURVE_DISPATCH(curve, {
-    msm::MsmPlan p = msm::MsmPlan::make(size, C::Fr::Config::kModulusBits);
+    msm::MsmPlan p = msm::MsmGpu<C>::default_plan(size);  // (mixed widths: the narrow windows' bits)
     *c = p.c;
     *windows = p.windows;
   }) GUARD_END

@@ -381,7 +381,7 @@ unsigned Groth16Prover<G1, G2>::ensure_table(msm::MsmGpu<G>& msm, FoldTable& tab
   if (len == 0) return 1;
   if (tab.fold != 0 && tab.want == fold && tab.c == c && tab.src == bases && tab.len == len) return tab.fold;
   const size_t old = tab.buf.capacity();
-  const unsigned f = msm.fit_fold(len, msm.plan_windows(len), fold, msm.run_bytes(len), old);
+  const unsigned f = msm.fit_fold(len, msm.fold_windows(len), fold, msm.run_bytes(len), old);
   tab.fold = 0;
   if (f > 1) {
     if (old < msm::MsmGpu<G>::fold_table_bytes(len, f)) tab.buf.release();  // (free it before the larger one)

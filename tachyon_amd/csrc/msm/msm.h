@@ -20,6 +20,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../common/hip_util.h"
@@ -28,19 +30,38 @@
 namespace tachyon_amd::msm {
 
 // MsmGpu::set_variant bits that exist (A/B tuning only; all compute the same MSM)
-constexpr int kMsmVariantMask = 0x3FFFFBF;  // bits 0-25 except 6 (21: a debug check, not a schedule)
+constexpr int kMsmVariantMask = 0x3FFFFBF | (1 << 27);  // bits 0-25 except 6 (21: a debug check), and 27
+// bit 27: the uniform window plan where the default would be mixed widths (A/B)
+constexpr int kMsmVariantUniformWindows = 1 << 27;
 // schedule of the last run (last_schedule()): the recode fused with the first
 // radix pass, the onesweep passes fed by the recode's digit counts, 7-byte LDS
 // staging in the recode scatter, the 29-bit-limb G1 accumulation, the lane-pair
 // G2 accumulation, the 28-bit-limb BLS12-381 G1 accumulation, the pre-derived
 // chain flags checked, the limb-field accumulation's entries staged in LDS
 constexpr unsigned kSchedFusedRecode = 1, kSchedRecodeFedSort = 2, kSchedNarrowStaging = 4, kSchedAcc29 = 8,
-                   kSchedLanePair = 16, kSchedAcc28 = 32, kSchedChainsChecked = 64, kSchedEntStaged = 128;
+                   kSchedLanePair = 16, kSchedAcc28 = 32, kSchedChainsChecked = 64, kSchedEntStaged = 128,
+                   kSchedMixedWindows = 256;  // ... and windows of two widths (MsmPlan::make_mixed)
+
+// Mixed-width keys are global bucket indices of at most kMixedKeyBits bits;
+// the all-ones key is reserved for a zero digit (it sorts last, no bucket).
+constexpr unsigned kMixedKeyBits = 24;
+constexpr uint32_t kMixedNoKey = (1u << kMixedKeyBits) - 1;
 
 struct MsmPlan {
-  unsigned c = 0;        // window bits
+  unsigned c = 0;        // window bits (mixed widths: the narrow windows', c_lo)
   unsigned windows = 0;  // W
-  unsigned buckets = 0;  // B = 2^(c-1) buckets per window (|digit| in [1, B])
+  unsigned buckets = 0;  // B = 2^(c-1) buckets per window (|digit| in [1, B]; a wide window has 2 B)
+  // Mixed widths (make_mixed): the top n_wide of the W windows are c + 1 bits
+  // wide, so that the widths add up to bits + 1 exactly; everything per window
+  // is a closed form of (c, n_wide, W).  mixed = false: W windows of c bits.
+  bool mixed = false;
+  unsigned n_wide = 0;
+  unsigned narrow() const { return windows - n_wide; }  // windows [0, narrow()) are c bits wide
+  unsigned width(unsigned w) const { return c + (mixed && w >= narrow() ? 1u : 0u); }
+  unsigned bit_offset(unsigned w) const { return w * c + (mixed && w > narrow() ? w - narrow() : 0u); }
+  // buckets before window w's (its key offset), in all at w = W
+  size_t bucket_offset(unsigned w) const { return (size_t)(w + (mixed && w > narrow() ? w - narrow() : 0u)) * buckets; }
+  size_t total_buckets() const { return mixed ? bucket_offset(windows) : (size_t)active() * buckets; }
   unsigned K = 0;        // entries per accumulation chunk
   unsigned K2 = 16;      // fan-in of the partial-reduction levels (4 for long chains at run time)
   unsigned levels = 0;   // number of K2 levels
@@ -54,14 +75,31 @@ struct MsmPlan {
   unsigned active() const { return w_end - w_begin; }
   static inline MsmPlan make(size_t n, unsigned scalar_bits, unsigned force_c = 0, unsigned w_begin = 0,
                              unsigned w_end = ~0u);
+  // W windows of floor((bits + 1) / W) bits and one more (all windows; throws
+  // where the layout is refused: mixed_layout_ok)
+  static inline MsmPlan make_mixed(size_t n, unsigned scalar_bits, unsigned W);
+  // Whether W mixed-width windows of a scalar_bits-bit scalar are a layout the
+  // kernels take: widths of 2 .. 26 bits and every bucket index below the
+  // reserved key, i.e. keys of kMixedKeyBits bits -- the fused low byte plus
+  // two radix places; a layout that needs a third place is refused.
+  static inline bool mixed_layout_ok(unsigned scalar_bits, unsigned W);
+  // running-sum segment lengths of `windows` windows of `buckets` buckets
+  // (window_sums_by_segments / window_sums_by_trees)
+  static inline unsigned seg_for(size_t windows, unsigned buckets);
+  static inline unsigned seg_tree_for(size_t windows, unsigned buckets);
+
+ private:
+  inline void size_for(size_t n);  // K, the join levels and the segment lengths of an n-point run
 };
 
 // Window size: more bits -> fewer windows (fewer madds, fewer sort passes)
 // but more buckets to reduce.  n*W madds dominate at large n; below ~2^20 the
 // latency of the bucket/window reduction sets a ~1 ms floor, which favours
 // few windows.  Table = fastest c of the BN254 G1 sweeps on MI355X
-// (tools/tune_msm.py); only c with a distinct window count
-// (W = ceil(255/c)) are candidates.  For another scalar width a c whose
+// (tools/tune_msm.py); among uniform widths only c with a distinct
+// window count (W = ceil(255/c)) are candidates -- windows of two widths
+// (MsmPlan::make_mixed, default_mixed_windows) reach the window counts in
+// between without a window spent on bits the scalar lacks.  For another scalar width a c whose
 // window count c - 1 also gives is one bit of buckets too many: BLS12-381's
 // 255-bit Fr has W = 16 at c = 16 and at c = 17, and c = 16 measured faster at
 // 2^22 / 2^23 (G1 12.8 vs 14.1 / 23.4 vs 25.5 ms, G2 31.7 vs 34.5 / 60.3 vs
@@ -84,6 +122,60 @@ inline MsmPlan MsmPlan::make(size_t n, unsigned scalar_bits, unsigned force_c, u
   p.buckets = 1u << (c - 1);
   p.w_end = std::min(w_end, p.windows);
   p.w_begin = std::min(w_begin, p.w_end);
+  p.size_for(n);
+  return p;
+}
+
+inline bool MsmPlan::mixed_layout_ok(unsigned scalar_bits, unsigned W) {
+  if (W < 1 || W > scalar_bits + 1) return false;
+  const unsigned c_lo = (scalar_bits + 1) / W, n_wide = scalar_bits + 1 - W * c_lo;
+  if (c_lo < 2 || c_lo + (n_wide ? 1 : 0) > 26) return false;
+  return ((uint64_t)(W + n_wide) << (c_lo - 1)) <= kMixedNoKey;  // the largest key is below the reserved one
+}
+
+inline MsmPlan MsmPlan::make_mixed(size_t n, unsigned scalar_bits, unsigned W) {
+  if (!mixed_layout_ok(scalar_bits, W))
+    throw std::runtime_error("tachyon_mi355x: " + std::to_string(W) + " mixed-width MSM windows refused (widths of 2 to "
+                             "26 bits, bucket keys of at most 24 bits)");
+  MsmPlan p;
+  p.mixed = true;
+  p.windows = W;
+  p.c = (scalar_bits + 1) / W;
+  p.n_wide = scalar_bits + 1 - W * p.c;
+  p.buckets = 1u << (p.c - 1);
+  p.w_begin = 0, p.w_end = W;
+  p.size_for(n);
+  return p;
+}
+
+inline unsigned MsmPlan::seg_for(size_t windows, unsigned buckets) {
+  // running-sum segment length: long segments amortise the (jL)*R fix-up, but
+  // small MSMs need >= ~48K segment threads to fill the chip (a 2^16 MSM with
+  // 64-bucket segments ran 208 threads of ~2000 serial mulmods each).
+  // TACHYON_MSM_SEG sweep (ms): 2^20 L = 8/16/32 2.83/2.97/3.29; 2^22 8/16/32
+  // 7.99/7.84/8.30; 2^24 16/32/64 26.3/26.2/26.3
+  const size_t nb = windows * buckets;
+  unsigned seg = 2;
+  while (seg < 64 && ((nb / (seg * 2)) >= 49152)) seg *= 2;
+  seg = std::min<unsigned>(buckets, seg);
+#ifdef TACHYON_TUNING_KNOBS
+  if (const char* e = getenv("TACHYON_MSM_SEG"); e && atoi(e) > 0)  // A/B override (tuning builds only)
+    seg = std::clamp<unsigned>(atoi(e), 2, buckets);
+#endif
+  return seg;
+}
+
+inline unsigned MsmPlan::seg_tree_for(size_t windows, unsigned buckets) {
+  // workgroup-tree reduction: no per-segment fix-up, so shorter segments (more
+  // threads, shorter serial chains) until ~128 K segment threads
+  const size_t nb = windows * buckets;
+  unsigned st = 2;
+  while (st < 64 && (nb / (st * 2)) >= 131072) st *= 2;
+  return std::min<unsigned>(buckets, st);
+}
+
+inline void MsmPlan::size_for(size_t n) {
+  MsmPlan& p = *this;
   size_t entries = (size_t)n * p.active();
   // One sort + one accumulation launch over all windows.  (Pipelining one
   // window at a time -- window w+1 sorting on a second stream while window w
@@ -119,25 +211,10 @@ inline MsmPlan MsmPlan::make(size_t n, unsigned scalar_bits, unsigned force_c, u
     maxchunks = (maxchunks + p.K2 - 1) / p.K2;
     ++p.levels;
   }
-  // running-sum segment length: long segments amortise the (jL)*R fix-up, but
-  // small MSMs need >= ~48K segment threads to fill the chip (a 2^16 MSM with
-  // 64-bucket segments ran 208 threads of ~2000 serial mulmods each).
-  // TACHYON_MSM_SEG sweep (ms): 2^20 L = 8/16/32 2.83/2.97/3.29; 2^22 8/16/32
-  // 7.99/7.84/8.30; 2^24 16/32/64 26.3/26.2/26.3
-  size_t nb = (size_t)p.active() * p.buckets;
-  unsigned seg = 2;
-  while (seg < 64 && ((nb / (seg * 2)) >= 49152)) seg *= 2;
-  p.seg = std::min<unsigned>(p.buckets, seg);
-  // workgroup-tree reduction: no per-segment fix-up, so shorter segments (more
-  // threads, shorter serial chains) until ~128 K segment threads
-  unsigned st = 2;
-  while (st < 64 && (nb / (st * 2)) >= 131072) st *= 2;
-  p.seg_tree = std::min<unsigned>(p.buckets, st);
-#ifdef TACHYON_TUNING_KNOBS
-  if (const char* e = getenv("TACHYON_MSM_SEG"); e && atoi(e) > 0)  // A/B override (tuning builds only)
-    p.seg = std::clamp<unsigned>(atoi(e), 2, p.buckets);
-#endif
-  return p;
+  // the window sums' segment lengths (mixed widths: window_sums takes them per
+  // width class, by the same rule)
+  p.seg = seg_for(p.active(), p.buckets);
+  p.seg_tree = seg_tree_for(p.active(), p.buckets);
 }
 
 // Per-phase device timings of the last run (ms), filled when profiling is on.
@@ -208,7 +285,21 @@ class MsmGpu {
   void fold_bases_groups(const void* bases, size_t len, size_t count, unsigned fold, void* out);
   std::vector<Point> run_groups_folded(const void* folded_bases, const void* scalars, size_t len, size_t count,
                                        unsigned fold);
-  unsigned plan_windows(size_t n) const;  // W of the plan for n points
+  unsigned plan_windows(size_t n) const;  // W of the plan a plain run of n points takes (mixed widths included)
+  unsigned fold_windows(size_t n) const;  // W of the uniform plan: what a fold divides
+  // The plan of a plain n-point run of a fresh context: the uniform plan of the
+  // size, or the mixed widths where they are the default.
+  static MsmPlan default_plan(size_t n) {
+    const unsigned W = default_mixed_windows(n);
+    return W ? MsmPlan::make_mixed(n, Fr::Config::kModulusBits, W) : MsmPlan::make(n, Fr::Config::kModulusBits);
+  }
+  // Mixed widths by default: BN254 G1 from 2^26 points (over 2^25), 12 windows
+  // of 21 and 22 bits for the 13 of 20 -- one window in thirteen less to
+  // recode, sort and accumulate for 2.3 x the buckets to reduce (DESIGN.md,
+  // MSM section; profiles/mixed_windows/ab.log).  0 = the uniform plan.
+  static unsigned default_mixed_windows(size_t n) {
+    return std::is_same_v<Curve, Bn254G1> && n > (size_t(1) << 25) ? 12u : 0u;
+  }
   unsigned batch_windows(size_t len) const {  // W of run_batch / run_groups over len-point MSMs
     const unsigned c = batch_window_bits(len);
     return (Fr::Config::kModulusBits + 1 + c - 1) / c;
@@ -239,6 +330,8 @@ class MsmGpu {
   static constexpr size_t kFoldChunkBytes = size_t(1) << 30;
 
   static Point combine_windows(const std::vector<Point>& window_sums, unsigned c);
+  // ... of a run's plan: its active windows, each doubled up by the width of the window below
+  static Point combine_windows(const std::vector<Point>& window_sums, const MsmPlan& plan);
   // Mixed additions per second (G/s) of this curve's accumulation field code
   // in registers on the current device -- no gathers, no run logic: the VALU
   // ceiling the bench prices the accumulation against, measured on the same
@@ -248,13 +341,24 @@ class MsmGpu {
   static double madd_ceiling(int field_bits);
 
   void set_force_window_bits(unsigned c) { force_c_ = c; }
+  // W windows of mixed widths for later plain runs (0 = off: the size's
+  // default).  Only a plain run takes them -- all windows, no batch, no fold,
+  // no forced window bits, one sort group: any other run throws while they are
+  // set.  A W the layout refuses (MsmPlan::mixed_layout_ok) throws here.
+  void set_mixed_windows(unsigned W) {
+    if (W && !MsmPlan::mixed_layout_ok(Fr::Config::kModulusBits, W))
+      (void)MsmPlan::make_mixed(1, Fr::Config::kModulusBits, W);  // throws, with the reason
+    mixed_w_ = W;
+  }
+  unsigned mixed_windows() const { return mixed_w_; }
   // kernel-variant bits for in-process A/B tuning (0 = default)
   // A/B tuning knobs (bits 0-5, 7-20, 22 -- the FIPS reductions instead of
   // the limb-field ones; see run_windows --, 23 two-level and 24 two-pass
   // window sums) and bit 21, a debug check (the small-MSM chain flags vs the
-  // accumulation's).  Every variant computes the same MSM; bit 6 (once a
-  // wrong-result gather-locality experiment) and anything above bit 24 are
-  // refused.
+  // accumulation's).  Bit 27: the uniform plan where windows of two widths are
+  // the size's default.  Every variant computes the same MSM; bit 6 (once a
+  // wrong-result gather-locality experiment), bit 26 and anything above bit 27
+  // are refused.
   void set_variant(int v) {
     if (v < 0 || (v & ~kMsmVariantMask)) throw std::runtime_error("tachyon_mi355x: unknown MSM variant bits");
     variant_ = v;
@@ -345,7 +449,8 @@ class MsmGpu {
     bool narrow, fused, own_sort;
     size_t scatter_lds;
   };
-  static SortShape sort_shape(const SortKnobs& k, unsigned c, unsigned Ws, unsigned W, unsigned G, size_t entries);
+  static SortShape sort_shape(const SortKnobs& k, unsigned c, unsigned Ws, unsigned W, unsigned G, size_t entries,
+                              bool mixed = false);
   size_t memory_divisions(size_t n, size_t resident_bytes) const;
   void ensure_group_events(unsigned groups);
   void build_chains(const Shape& s, const Buffers& b);
@@ -356,6 +461,7 @@ class MsmGpu {
   bool own_stream_ = false;
   bool profile_ = false;
   unsigned force_c_ = 0;
+  unsigned mixed_w_ = 0;  // set_mixed_windows
   int variant_ = 0;
   MsmTimings timings_;
   DeviceBuffer bases_, scalars_, ents_, ents2_, sort_tmp_, scan_tmp_, check_;

@@ -79,16 +79,10 @@ __global__ __launch_bounds__(kBlock, AccWaves<Curve>::value) void seg_acc_kernel
   if (g0 >= gend) return;
   const uint64_t g1 = min(g0 + K, gend);
   const uint64_t t = tbase + tl;  // global thread slot (pieces/flags are in entry order)
-  const uint32_t dmask = (1u << c) - 1;
-  // bucket id (w * 2^(c-1) + |digit| - 1) of a combined key, or none for digit 0
-  auto bucket_of_key = [&](uint32_t key) -> uint32_t {
-    uint32_t d = key & dmask;
-    return d ? ((key >> c) << (c - 1)) + (d - 1) : kNoBucket;
-  };
   // neighbours outside this launch's entry range belong to other windows
   // (possibly not sorted yet): they never share a bucket
-  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1])) : kNoBucket;
-  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1])) : kNoBucket;
+  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1]), c) : kNoBucket;
+  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1]), c) : kNoBucket;
 
   uint32_t flags = 0, runs = 0, cur = kNoBucket;
   XYZZ<F> acc = XYZZ<F>::zero();
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(kBlock, AccWaves<Curve>::value) void seg_acc_kernel
     if constexpr (kPrefetchBase) Pn = hbases[entry_val(e1) & idx_mask];
     else P = hbases[entry_val(e0) & idx_mask];
     const uint32_t k0 = entry_key(e0), v0 = entry_val(e0);
-    const uint32_t b = bucket_of_key(k0);
+    const uint32_t b = bucket_of_key(k0, c);
     if (b != kNoBucket) {
       if (b != cur) {
         if (cur != kNoBucket) {  // close a run that is not the last one
@@ -373,13 +367,8 @@ __device__ __forceinline__ void seg_acc_limb_body(const Affine<typename Pol::Fq>
   if (g0 >= gend) return;
   const uint64_t g1 = min(g0 + K, gend);
   const uint64_t t = tbase + tl;
-  const uint32_t dmask = (1u << c) - 1;
-  auto bucket_of_key = [&](uint32_t key) -> uint32_t {
-    uint32_t d = key & dmask;
-    return d ? ((key >> c) << (c - 1)) + (d - 1) : kNoBucket;
-  };
-  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1])) : kNoBucket;
-  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1])) : kNoBucket;
+  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1]), c) : kNoBucket;
+  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1]), c) : kNoBucket;
   uint32_t flags = 0, runs = 0, cur = kNoBucket;
   Acc acc{};  // (any defined value: the stores mask it while acc_zero)
   bool acc_zero = true;
@@ -492,7 +481,7 @@ __device__ __forceinline__ void seg_acc_limb_body(const Affine<typename Pol::Fq>
       P = bases[entry_val(e0) & idx_mask];
     }
     const uint32_t k0 = entry_key(e0), v0 = entry_val(e0);
-    const uint32_t b = bucket_of_key(k0);
+    const uint32_t b = bucket_of_key(k0, c);
     if (b != kNoBucket) {
       if (b != cur) {
         if (cur != kNoBucket) {
@@ -592,13 +581,8 @@ __global__ __launch_bounds__(kBlock) void seg_acc_pair_kernel(const Affine<typen
   if (g0 >= gend) return;  // both lanes of the pair
   const uint64_t g1 = min(g0 + K, gend);
   const uint64_t t = tbase + tl;
-  const uint32_t dmask = (1u << c) - 1;
-  auto bucket_of_key = [&](uint32_t key) -> uint32_t {
-    uint32_t d = key & dmask;
-    return d ? ((key >> c) << (c - 1)) + (d - 1) : kNoBucket;
-  };
-  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1])) : kNoBucket;
-  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1])) : kNoBucket;
+  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1]), c) : kNoBucket;
+  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1]), c) : kNoBucket;
   // component views: a point is {x.c0, x.c1, y.c0, y.c1}, an XYZZ {x.c0, x.c1, ..., zzz.c1}
   const Fb* comp = reinterpret_cast<const Fb*>(bases);
   Fb* bsum = reinterpret_cast<Fb*>(bucket_sum);
@@ -625,7 +609,7 @@ __global__ __launch_bounds__(kBlock) void seg_acc_pair_kernel(const Affine<typen
   for (uint64_t g = g0; g < g1; ++g) {
     const uint64_t e1 = (g + 1 < g1) ? ents[g + 1] : 0;
     const uint32_t k0 = entry_key(e0), v0 = entry_val(e0);
-    const uint32_t b = bucket_of_key(k0);
+    const uint32_t b = bucket_of_key(k0, c);
     if (b != kNoBucket) {
       const Fb* pt = comp + 4 * (size_t)(v0 & idx_mask);
       H px{pt[h]}, py{pt[2 + h]};
@@ -735,13 +719,8 @@ __global__ __launch_bounds__(kBlock) void seg_acc_pair_limb_kernel(const Affine<
   if (g0 >= gend) return;  // both lanes of the pair
   const uint64_t g1 = min(g0 + K, gend);
   const uint64_t t = tbase + tl;
-  const uint32_t dmask = (1u << c) - 1;
-  auto bucket_of_key = [&](uint32_t key) -> uint32_t {
-    uint32_t d = key & dmask;
-    return d ? ((key >> c) << (c - 1)) + (d - 1) : kNoBucket;
-  };
-  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1])) : kNoBucket;
-  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1])) : kNoBucket;
+  const uint32_t prev_b = g0 > gbeg ? bucket_of_key(entry_key(ents[g0 - 1]), c) : kNoBucket;
+  const uint32_t next_b = (g1 < gend) ? bucket_of_key(entry_key(ents[g1]), c) : kNoBucket;
   const Fb* comp = reinterpret_cast<const Fb*>(bases);
   Fb* bsum = reinterpret_cast<Fb*>(bucket_sum);
   Fb* pcs = reinterpret_cast<Fb*>(pieces);
@@ -807,7 +786,7 @@ __global__ __launch_bounds__(kBlock) void seg_acc_pair_limb_kernel(const Affine<
       e1 = (g + 1 < g1) ? ents[g + 1] : 0;
     }
     const uint32_t k0 = entry_key(e0), v0 = entry_val(e0);
-    const uint32_t b = bucket_of_key(k0);
+    const uint32_t b = bucket_of_key(k0, c);
     if (b != kNoBucket) {
       const Fb* pt = comp + 4 * (size_t)(v0 & idx_mask);
       const Fb px = pt[h];

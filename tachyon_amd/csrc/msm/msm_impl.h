@@ -123,13 +123,19 @@ struct MsmGpu<Curve>::Shape {
   // the scalar (the recode's carry chain), the range starting at window
   // w_begin; W = the window sums this run computes (make_shape)
   unsigned Ws, Wt, w_begin, W, B, c;
+  // mixed widths (MsmPlan::make_mixed): windows [narrow, W) are c + 1 bits wide
+  // with 2 B buckets, keys are bucket indices; uniform: narrow = ~0u.  key_c is
+  // what bucket_of_key decodes the keys by (c, or 0 for the mixed keys)
+  bool mixed;
+  uint32_t narrow;
+  unsigned key_c;
   uint32_t K;
   unsigned K2, seg, seg_tree;  // the plan's join fan-in and window-sum segment lengths
   unsigned G, ngroups;
   size_t epw;      // entries per key window's share of the array (n without a batch)
   size_t T;        // accumulation threads over all groups
   size_t entries;  // n * Ws
-  size_t nb;       // W * B buckets
+  size_t nb;       // W * B buckets (mixed widths: narrow * B + (W - narrow) * 2 B)
   uint32_t fold_w, glen, gstep, fold_n;  // recode_scalar's batch / fold arguments
   SlotBytes sb;
   SortShape ss;
@@ -196,7 +202,10 @@ typename MsmGpu<Curve>::Shape MsmGpu<Curve>::make_shape(size_t n, const MsmPlan&
   s.gstep = batch_distinct_ ? 0u : s.glen;  // shared bases (run_batch) or one array per MSM (run_groups)
   s.fold_n = s.gstep ? s.glen : (uint32_t)n;  // points per fold copy
   s.entries = n * s.Ws;
-  s.nb = (size_t)s.W * s.B;
+  s.mixed = plan.mixed;
+  s.narrow = plan.mixed ? plan.narrow() : ~0u;
+  s.key_c = plan.mixed ? 0u : s.c;
+  s.nb = plan.mixed ? plan.total_buckets() : (size_t)s.W * s.B;
   if (n >= (size_t(1) << 31)) throw std::runtime_error("tachyon_mi355x: MSM size must be < 2^31 per device");
   if (((uint64_t)s.W << s.c) > (uint64_t(1) << 32))  // 32-bit keys (window << c | digit)
     throw std::runtime_error("tachyon_mi355x: too many windows for 32-bit bucket keys (MSM batch too large)");
@@ -220,7 +229,7 @@ typename MsmGpu<Curve>::Shape MsmGpu<Curve>::make_shape(size_t n, const MsmPlan&
   // where the reductions read it (slot_bytes; work_bytes estimates by the same rule)
   s.sb = slot_bytes(acc_, variant_);
   // the sort's shape (sort_shape: work_bytes sizes the sort scratch by the same rule)
-  s.ss = sort_shape(sort_, s.c, s.Ws, s.W, s.G, s.entries);
+  s.ss = sort_shape(sort_, s.c, s.Ws, s.W, s.G, s.entries, s.mixed);
   // Where the chain tables (and the join levels' offsets) are built -- they
   // depend only on the sorted keys (chain_flags_kernel), so they need not wait
   // for the accumulation:
@@ -315,7 +324,7 @@ uint32_t* MsmGpu<Curve>::recode(const Shape& s, const Buffers& b, const Fr* d_sc
     uint32_t* btotal = bcpre + (size_t)bchunks * 256;
     hipLaunchKernelGGL(recode_hist_kernel<Fr>, dim3(nblocks), dim3(kBlock), 0, stream_, d_scalars, n, s.c, s.Wt,
                        s.w_begin, s.Ws, nblocks, spt, later_places, hist, later, reinterpret_cast<uint4*>(b.bucket_sum),
-                       s.nb * s.sb.slot / 16, s.glen, s.gstep, s.fold_w, s.fold_n);
+                       s.nb * s.sb.slot / 16, s.glen, s.gstep, s.fold_w, s.fold_n, s.narrow);
     TA_HIP(hipGetLastError());
     if (later_places > 0) {
       digit_off = digit_cnt + 2 * 256;
@@ -343,10 +352,10 @@ uint32_t* MsmGpu<Curve>::recode(const Shape& s, const Buffers& b, const Fr* d_sc
       scatter_lds_set_[ss.narrow ? 1 : 0] = true;
     }
     hipLaunchKernelGGL(scatter, dim3(nblocks), dim3(kBlock), ss.scatter_lds, stream_, d_scalars, n, s.c, s.Wt,
-                       s.w_begin, s.Ws, nblocks, spt, hist, hoff, dst, s.glen, s.gstep, s.fold_w, s.fold_n);
+                       s.w_begin, s.Ws, nblocks, spt, hist, hoff, dst, s.glen, s.gstep, s.fold_w, s.fold_n, s.narrow);
   } else {
     hipLaunchKernelGGL(recode_kernel<Fr>, dim3(grid_for(s.n)), dim3(kBlock), 0, stream_, d_scalars, n, s.c, s.Wt,
-                       s.w_begin, s.Ws, b.ents, s.glen, s.gstep, s.fold_w, s.fold_n);
+                       s.w_begin, s.Ws, b.ents, s.glen, s.gstep, s.fold_w, s.fold_n, s.narrow);
   }
   TA_HIP(hipGetLastError());
   // every bucket without an entry stays the identity (the fused recode clears them)
@@ -421,8 +430,8 @@ void MsmGpu<Curve>::build_chains(const Shape& s, const Buffers& b) {
 // chain tables before the accumulation; in-stream, every level's offsets too.
 template <class Curve>
 void MsmGpu<Curve>::early_chain_tables(const Shape& s, const Buffers& b, size_t e0, size_t ecount) {
-  hipLaunchKernelGGL(chain_flags_kernel, dim3(grid_for(s.T)), dim3(kBlock), 0, stream_, b.ents2, s.c, (uint64_t)e0,
-                     (uint64_t)(e0 + ecount), s.K, (uint32_t)s.T, b.cflags, b.clast);
+  hipLaunchKernelGGL(chain_flags_kernel, dim3(grid_for(s.T)), dim3(kBlock), 0, stream_, b.ents2, s.key_c,
+                     (uint64_t)e0, (uint64_t)(e0 + ecount), s.K, (uint32_t)s.T, b.cflags, b.clast);
   TA_HIP(hipGetLastError());
   build_chains(s, b);
   if (s.chain_mode == kChainsInStream) {
@@ -502,7 +511,7 @@ void MsmGpu<Curve>::accumulate(const Shape& s, const Buffers& b, const Aff* d_ba
   const int ent_mode = (variant_ & (1u << 25)) ? 0 : (s.K % 2 == 0 && e0 % 2 == 0) ? 2 : 1;
   const AccLaunch a = acc_launch(s.sb.raw, ent_mode);
   last_schedule_ |= a.sched;
-  hipLaunchKernelGGL(a.kernel, dim3(grid_for(a.lanes * Tg)), dim3(kBlock), 0, stream_, d_bases, b.ents2, s.c,
+  hipLaunchKernelGGL(a.kernel, dim3(grid_for(a.lanes * Tg)), dim3(kBlock), 0, stream_, d_bases, b.ents2, s.key_c,
                      (uint64_t)e0, (uint64_t)(e0 + ecount), (uint64_t)tbase, s.K, ~kSignBit, b.bucket_sum, b.pieces,
                      b.tflags, b.tlast);
   TA_HIP(hipGetLastError());
@@ -821,8 +830,34 @@ void MsmGpu<Curve>::window_sums_by_segments(const Shape& s, const Buffers& b, co
   }
 }
 
+// Mixed widths: one pass per width class over the class's contiguous buckets
+// -- B is uniform inside a class, so the kernels are the uniform ones, each
+// class with the segment lengths of its own window and bucket counts.
 template <class Curve>
 void MsmGpu<Curve>::window_sums(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows) {
+  if (s.mixed) {
+    const unsigned classes[2][3] = {{0, s.narrow, s.B}, {s.narrow, s.W - s.narrow, 2 * s.B}};  // first window, windows, B
+    // the segment sums of both classes share seg_a_ / seg_b_: sized for the larger before either is enqueued
+    size_t seg_sums = 0;
+    for (const auto& cl : classes) seg_sums = std::max(seg_sums, (size_t)cl[1] * (cl[2] / MsmPlan::seg_for(cl[1], cl[2])));
+    seg_a_.ensure(seg_sums * sizeof(Point));
+    seg_b_.ensure(seg_sums * sizeof(Point));
+    for (const auto& cl : classes) {
+      if (cl[1] == 0) continue;
+      Shape sc = s;
+      Buffers bc = b;
+      sc.mixed = false;
+      sc.W = cl[1], sc.B = cl[2];
+      sc.seg = MsmPlan::seg_for(cl[1], cl[2]);
+      if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>)  // (as run_plan's G2 rule)
+        sc.seg = std::min(sc.B, std::min(128u, sc.seg * 2));
+      sc.seg_tree = MsmPlan::seg_tree_for(cl[1], cl[2]);
+      bc.bucket_sum = reinterpret_cast<Point*>(reinterpret_cast<char*>(b.bucket_sum) +
+                                               (size_t)cl[0] * s.B * s.sb.slot);
+      window_sums(sc, bc, rk, d_windows + cl[0]);
+    }
+    return;
+  }
   if (rk.seg1 && (variant_ & (1 << 23)) && !acc_.tree_reduce) return window_sums_two_level(s, b, rk, d_windows);
   if (acc_.tree_reduce) return window_sums_by_trees(s, b, d_windows);
   if constexpr (std::is_same_v<Curve, Bn254G1>) {
@@ -850,7 +885,7 @@ void MsmGpu<Curve>::enqueue(const Aff* d_bases, const Fr* d_scalars, size_t n, c
   const Buffers b = carve(s);
   const ReduceKernels rk = reduce_kernels(s.sb.raw);
   last_schedule_ = (s.ss.fused ? kSchedFusedRecode : 0u) | (s.ss.own_sort ? kSchedRecodeFedSort : 0u) |
-                   (s.ss.fused && s.ss.narrow ? kSchedNarrowStaging : 0u);
+                   (s.ss.fused && s.ss.narrow ? kSchedNarrowStaging : 0u) | (s.mixed ? kSchedMixedWindows : 0u);
   if (profile_) TA_HIP(hipEventRecord(ev_[kMarkUploaded], stream_));
   uint32_t* digit_off = recode(s, b, d_scalars);
   TA_HIP(hipEventRecord(ev_[kMarkRecoded], stream_));  // recode done (also the profile mark)
@@ -877,6 +912,9 @@ template <class Curve>
 void MsmGpu<Curve>::run_windows(const void* bases, const void* scalars, size_t n, std::vector<Point>* out,
                                 MsmPlan* plan_out) {
   MsmPlan plan = run_plan(n, force_c_);
+  if (mixed_w_ && !plan.mixed)  // asked for both: an error, not a silent uniform run
+    throw std::runtime_error("tachyon_mi355x: mixed-width MSM windows are set: no window range, batch, fold, forced "
+                             "window bits or window groups with them");
   // what the variant bits select (sort_knobs, acc_fields), decoded once per run
   sort_ = sort_knobs(variant_);
   acc_ = acc_fields(variant_);
@@ -942,6 +980,20 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::combine_windows(const std::vector<P
   for (size_t w = ws.size(); w-- > 0;) {
     if (w + 1 < ws.size())
       for (unsigned k = 0; k < c; ++k) total = total.dbl();
+    total = total + ws[w];
+  }
+  return total;
+}
+
+// ... over a run's active windows: the doublings between two windows are the
+// width of the lower one (uniform plans: c)
+template <class Curve>
+typename MsmGpu<Curve>::Point MsmGpu<Curve>::combine_windows(const std::vector<Point>& ws, const MsmPlan& plan) {
+  if (!plan.mixed) return combine_windows(ws, plan.c);
+  Point total = Point::zero();
+  for (size_t w = ws.size(); w-- > 0;) {
+    if (w + 1 < ws.size())
+      for (unsigned k = 0; k < plan.width((unsigned)w); ++k) total = total.dbl();
     total = total + ws[w];
   }
   return total;
@@ -1028,7 +1080,7 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::run_host_pipelined(const void* base
     if (!len) continue;
     TA_HIP(hipStreamWaitEvent(stream_, chunk_ev_[k], 0));
     run_windows(d_b + lo, d_s + lo, len, &ws, &plan);
-    total = total + combine_windows(ws, plan.c);
+    total = total + combine_windows(ws, plan);
   }
   copier.join();
   if (copy_error) std::rethrow_exception(copy_error);
@@ -1048,6 +1100,15 @@ bool MsmGpu<Curve>::window_sums_by_scan(const AccFields& f, unsigned buckets) {
 template <class Curve>
 MsmPlan MsmGpu<Curve>::run_plan(size_t n, unsigned c) const {
   MsmPlan plan = MsmPlan::make(n, Fr::Config::kModulusBits, c, range_begin_, range_end_);
+  // Mixed widths: for a plain run only -- all windows, one MSM, no fold, no
+  // forced window bits, one sort group.  Set explicitly (set_mixed_windows),
+  // any other run is an error (run_windows throws); as the size's default, the
+  // other runs keep the uniform plan, and set_variant bit 27 restores it for
+  // the plain run (A/B).
+  const bool plain = range_begin_ == 0 && range_end_ == ~0u && batch_ == 1 && fold_ == 1 && c == 0 &&
+                     (((variant_ >> 2) & 3) == 0 || ((variant_ >> 2) & 3) == 3);
+  const unsigned mixed_w = mixed_w_ ? mixed_w_ : (variant_ & kMsmVariantUniformWindows) ? 0u : default_mixed_windows(n);
+  if (mixed_w && plain) plan = MsmPlan::make_mixed(n, Fr::Config::kModulusBits, mixed_w);
   // G2: running-sum segments twice the G1 rule's length -- a G2 fix-up costs
   // more against the latency-bound loop (BLS12-381 G2 2^24 reduction 13.7 ->
   // 13.0 ms at L = 128, BN254 G2 2^22 1.75 -> 1.64 ms at L = 32;
@@ -1056,7 +1117,7 @@ MsmPlan MsmGpu<Curve>::run_plan(size_t n, unsigned c) const {
 #ifdef TACHYON_TUNING_KNOBS
     if (!getenv("TACHYON_MSM_SEG"))
 #endif
-      plan.seg = std::min(plan.buckets, std::min(128u, plan.seg * 2));
+      if (!plan.mixed) plan.seg = std::min(plan.buckets, std::min(128u, plan.seg * 2));
   }
   switch (variant_ & 3) {  // accumulation chunk experiments
     case 1: plan.K = std::min(2048u, plan.K * 2); break;
@@ -1085,14 +1146,17 @@ typename MsmGpu<Curve>::SortKnobs MsmGpu<Curve>::sort_knobs(int variant) {
 }
 
 // How the entries of a run are sorted: c window bits, Ws windows per scalar,
-// W key windows in groups of G, `entries` in all.
+// W key windows in groups of G, `entries` in all (`mixed`: bucket-index keys).
 template <class Curve>
 typename MsmGpu<Curve>::SortShape MsmGpu<Curve>::sort_shape(const SortKnobs& k, unsigned c, unsigned Ws, unsigned W,
-                                                            unsigned G, size_t entries) {
+                                                            unsigned G, size_t entries, bool mixed) {
   SortShape s;
   unsigned wbits = 0;
   while ((1u << wbits) < W) ++wbits;
   s.key_bits = (G == 1) ? c : c + wbits;  // the window bits only matter within a multi-window group
+  // mixed widths: the keys are bucket indices and the largest key is the
+  // reserved one of the zero digits, all ones over kMixedKeyBits
+  if (mixed) s.key_bits = kMixedKeyBits;
   // recode fused with the first (low byte) radix pass; one sort group only
   // (the scatter stages a block's spt x 256 x W entries in LDS, <= 128 KiB)
   s.spt = k.spt;
@@ -1176,15 +1240,16 @@ size_t MsmGpu<Curve>::work_bytes(size_t n, unsigned c, size_t batch) const {
   // scatter past 128 KiB of LDS: many narrow windows; set_variant bits 7, 10):
   // its scratch holds another copy of the entries
   const unsigned W = (unsigned)(p.active() * batch), G = batch > 1 ? W : std::max(1u, std::min(p.group, W));
-  if (!sort_shape(sort_knobs(variant_), p.c, p.active(), W, G, entries).own_sort) bytes += entries * 8;
+  if (!sort_shape(sort_knobs(variant_), p.c, p.active(), W, G, entries, p.mixed).own_sort) bytes += entries * 8;
   const SlotBytes sb = slot_bytes(acc_fields(variant_), variant_);
   const size_t slot = sb.slot;
   bytes += 2 * T * slot + (2 * T / kJoinFanLong + T + 2) * sb.lvl_slot;     // pieces + first join level
   bytes += (T + 2) * 4 * 11;                                               // flags (x2), last bucket (x2), chain tables
   bytes += (T + 2) * 4 * 12;                                               // join-level offsets (<= 12 levels of <= T chains)
   // (a batch of `batch` MSMs over n points in all keeps a block of windows per MSM)
-  bytes += batch * p.active() * p.buckets * slot;                           // bucket sums
+  bytes += batch * p.total_buckets() * slot;                                // bucket sums
   // segment sums (x2), where the window sums are not one scan launch per window
+  // (mixed widths: at most this, the classes share them)
   if (!window_sums_by_scan(acc_fields(variant_), p.buckets))
     bytes += 2 * batch * p.active() * (p.buckets / p.seg) * sizeof(Point);
   return bytes + bytes / 10;
@@ -1279,7 +1344,7 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::run(const void* bases, const void* 
   MsmPlan plan;
   if (divisions == 1) {
     run_windows(bases, scalars, n, &ws, &plan);
-    return combine_windows(ws, plan.c);
+    return combine_windows(ws, plan);
   }
   // device-resident inputs larger than the working memory: consecutive point
   // chunks, results added (the kParallelTerm sum, pippenger_adapter.h:82-113)
@@ -1289,7 +1354,7 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::run(const void* bases, const void* 
   for (size_t lo = 0; lo < n; lo += step) {
     const size_t len = std::min(step, n - lo);
     run_windows(static_cast<const Aff*>(bases) + lo, static_cast<const Fr*>(scalars) + lo, len, &ws, &plan);
-    total = total + combine_windows(ws, plan.c);
+    total = total + combine_windows(ws, plan);
   }
   return total;
 }
@@ -1317,6 +1382,11 @@ const typename MsmGpu<Curve>::Aff* MsmGpu<Curve>::affine_bases(const void* bases
 
 template <class Curve>
 unsigned MsmGpu<Curve>::plan_windows(size_t n) const {
+  return run_plan(n, force_c_).windows;
+}
+
+template <class Curve>
+unsigned MsmGpu<Curve>::fold_windows(size_t n) const {
   return MsmPlan::make(n, Fr::Config::kModulusBits, force_c_).windows;
 }
 
@@ -1391,7 +1461,7 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::run_folded(const void* folded_bases
   std::vector<Point> ws;
   MsmPlan plan;
   run_windows(folded_bases, scalars, n, &ws, &plan);
-  return combine_windows(ws, plan.c);
+  return combine_windows(ws, plan);
 }
 
 // `count` MSMs over the same `len` device-resident bases in one recode, sort,
@@ -1495,7 +1565,7 @@ std::vector<typename MsmGpu<Curve>::Point> MsmGpu<Curve>::run_batch_impl(const v
   auto combine = [&](size_t g0, size_t g1) {
     for (size_t g = g0; g < g1; ++g) {
       std::vector<Point> one(ws.begin() + g * Ws, ws.begin() + (g + 1) * Ws);
-      res[g] = combine_windows(one, plan.c);
+      res[g] = combine_windows(one, plan);
     }
   };
   const size_t nth = std::min<size_t>({count / 4, 16, std::max(1u, std::thread::hardware_concurrency())});
@@ -1549,7 +1619,7 @@ typename MsmGpu<Curve>::Point MsmGpu<Curve>::run_window_range(const void* bases,
     const size_t len = std::min(step, n - lo);
     run_windows(static_cast<const Aff*>(bases) + lo, static_cast<const Fr*>(scalars) + lo, len, &ws, &plan);
     if (plan.active() == 0) return Point::zero();
-    Point p = combine_windows(ws, plan.c);
+    Point p = combine_windows(ws, plan);
     for (unsigned k = 0; k < plan.c * plan.w_begin; ++k) p = p.dbl();
     total = total + p;
   }

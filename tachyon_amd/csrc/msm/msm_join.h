@@ -48,11 +48,7 @@ __global__ __launch_bounds__(kBlock) void chain_flags_kernel(const uint64_t* __r
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
   if (t >= T) return;
   const uint64_t g0 = gbeg + (uint64_t)t * K, g1 = min(g0 + K, gend);
-  const uint32_t dmask = (1u << c) - 1;
-  auto bucket = [&](uint64_t g) -> uint32_t {
-    const uint32_t key = entry_key(ents[g]), d = key & dmask;
-    return d ? ((key >> c) << (c - 1)) + (d - 1) : kNoBucket;
-  };
+  auto bucket = [&](uint64_t g) -> uint32_t { return bucket_of_key(entry_key(ents[g]), c); };
   const uint32_t prev_b = g0 > gbeg ? bucket(g0 - 1) : kNoBucket;
   const uint32_t next_b = g1 < gend ? bucket(g1) : kNoBucket;
   uint32_t first = bucket(g0), last = bucket(g1 - 1);

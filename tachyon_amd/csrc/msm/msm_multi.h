@@ -82,6 +82,9 @@ class MsmMultiDevice {
   void set_force_window_bits(unsigned c) {
     for (auto& s : shards_) s->msm->set_force_window_bits(c);
   }
+  void set_mixed_windows(unsigned W) {
+    for (auto& s : shards_) s->msm->set_mixed_windows(W);
+  }
   void set_variant(int v) {
     for (auto& s : shards_) s->msm->set_variant(v);
   }
@@ -90,6 +93,7 @@ class MsmMultiDevice {
   }
   void copy_settings(const MsmGpu<Curve>& from) {
     set_force_window_bits(from.force_window_bits());
+    set_mixed_windows(from.mixed_windows());
     set_variant(from.variant());
     set_profile(from.profile());
   }

@@ -28,16 +28,22 @@ template <class Fr, class Emit>
 // 2^(k c fold_w) P): window w goes to key window w mod fold_w (of MSM g's
 // block g fold_w in a batch) and to copy w / fold_w, base index
 // vi + (w / fold_w) fold_n (fold_n = the length of one copy).
+// narrow < W (mixed widths, MsmPlan::make_mixed: a plain run, all windows, no
+// batch, no fold): windows [narrow, W) are c + 1 bits wide and the key is the
+// bucket's index over all windows, koff(w) + |digit| - 1, with koff(w) = (w +
+// max(0, w - narrow)) 2^(c-1) buckets below window w; a zero digit gets the
+// reserved key kMixedNoKey (it sorts last).  bucket_of_key decodes both forms.
 __device__ __forceinline__ void recode_scalar(const Fr& scalar, uint32_t i, unsigned c, unsigned W, unsigned w0,
                                               unsigned wr, Emit emit, uint32_t glen = 0, uint32_t gstep = 0,
-                                              uint32_t fold_w = 0, uint32_t fold_n = 0) {
+                                              uint32_t fold_w = 0, uint32_t fold_n = 0, uint32_t narrow = ~0u) {
   constexpr int N = Fr::N;
   Fr s = scalar.from_mont();
   uint32_t limbs[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) limbs[k] = s.v[k];
-  const uint32_t mask = (1u << c) - 1;
-  const uint32_t half = 1u << (c - 1);
+  const unsigned c_lo = c;
+  uint32_t mask = (1u << c) - 1;
+  uint32_t half = 1u << (c - 1);
   uint32_t gw = 0, vi = i;
   if (glen) {
     const uint32_t g = i / glen;
@@ -46,6 +52,11 @@ __device__ __forceinline__ void recode_scalar(const Fr& scalar, uint32_t i, unsi
   }
   uint32_t carry = 0;
   for (unsigned w = 0; w < w0 + wr; ++w) {
+    if (w == narrow) {  // the wide windows from here on
+      c = c_lo + 1;
+      mask = (1u << c) - 1;
+      half = 1u << (c - 1);
+    }
     uint32_t coeff = (limbs[0] & mask) + carry;
     // shift the scalar right by c (c < 32), constant-indexed limbs only: one
     // funnel shift (v_alignbit_b32) per limb
@@ -62,7 +73,10 @@ __device__ __forceinline__ void recode_scalar(const Fr& scalar, uint32_t i, unsi
       key = coeff;  // top digit, carry folded in, non-negative
       sign = 0;
     }
-    if (fold_w) {
+    if (narrow != ~0u) {
+      const uint32_t koff = (w + (w > narrow ? w - narrow : 0u)) << (c_lo - 1);
+      emit(w, key ? koff + key - 1 : kMixedNoKey, vi | sign);
+    } else if (fold_w) {
       const uint32_t part = w / fold_w;
       emit(w, ((gw + w - part * fold_w) << c) | key, (vi + part * fold_n) | sign);
     } else if (w >= w0) {
@@ -75,17 +89,27 @@ __device__ __forceinline__ uint64_t make_entry(uint32_t key, uint32_t val) { ret
 __device__ __forceinline__ uint32_t entry_key(uint64_t e) { return (uint32_t)(e >> 32); }
 __device__ __forceinline__ uint32_t entry_val(uint64_t e) { return (uint32_t)e; }
 
+// The bucket of a key, or kNoBucket for a zero digit.  c > 0: the combined key
+// window << c | |digit| of uniform c-bit windows, bucket w 2^(c-1) + |digit| -
+// 1.  c == 0 (mixed widths): the key is the bucket, the reserved key is none.
+// c is a kernel argument, so the choice is wave-uniform.
+__device__ __forceinline__ uint32_t bucket_of_key(uint32_t key, uint32_t c) {
+  if (c == 0) return key == kMixedNoKey ? kNoBucket : key;
+  const uint32_t d = key & ((1u << c) - 1);
+  return d ? ((key >> c) << (c - 1)) + (d - 1) : kNoBucket;
+}
+
 template <class Fr>
 __global__ __launch_bounds__(kBlock) void recode_kernel(const Fr* __restrict__ scalars, uint32_t n,
                                                         unsigned c, unsigned W, unsigned w0, unsigned wr,
                                                         uint64_t* __restrict__ ents, uint32_t glen, uint32_t gstep,
-                                                        uint32_t fold_w, uint32_t fold_n) {
+                                                        uint32_t fold_w, uint32_t fold_n, uint32_t narrow) {
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   recode_scalar(
       scalars[i], i, c, W, w0, wr,
       [&](unsigned w, uint32_t key, uint32_t val) { ents[(size_t)w * n + i] = make_entry(key, val); }, glen, gstep,
-      fold_w, fold_n);
+      fold_w, fold_n, narrow);
 }
 
 // Recode fused with the first radix pass (key bits 0..7), in two launches:
@@ -135,7 +159,8 @@ __global__ __launch_bounds__(kBlock) void recode_hist_kernel(const Fr* __restric
                                                              uint32_t* __restrict__ hist,
                                                              uint32_t* __restrict__ later,
                                                              uint4* __restrict__ zero, size_t zero_n, uint32_t glen,
-                                                             uint32_t gstep, uint32_t fold_w, uint32_t fold_n) {
+                                                             uint32_t gstep, uint32_t fold_w, uint32_t fold_n,
+                                                             uint32_t narrow) {
   // cnt2: the third place's counts (key bits 16..23) in four copies, one per
   // lane & 3, 264 words apart: those bits are the window (the same in every
   // lane of a step) and the digit's top bits, a handful of values per wave --
@@ -181,7 +206,7 @@ __global__ __launch_bounds__(kBlock) void recode_hist_kernel(const Fr* __restric
             }
           }
         }
-      }, glen, gstep, fold_w, fold_n);
+      }, glen, gstep, fold_w, fold_n, narrow);
   }
   __syncthreads();
   hist[(size_t)blockIdx.x * 256 + t] = cnt[0][t];  // one coalesced 1 KiB row per block
@@ -300,7 +325,8 @@ __global__ __launch_bounds__(kBlock) void recode_scatter_kernel(const Fr* __rest
                                                                 const uint32_t* __restrict__ hist,
                                                                 const uint32_t* __restrict__ off,
                                                                 uint64_t* __restrict__ ents, uint32_t glen,
-                                                                uint32_t gstep, uint32_t fold_w, uint32_t fold_n) {
+                                                                uint32_t gstep, uint32_t fold_w, uint32_t fold_n,
+                                                                uint32_t narrow) {
   // the block's entries are binned in LDS first, then written out bin run by
   // bin run, so consecutive lanes store to consecutive addresses
   extern __shared__ uint64_t lds_u64[];
@@ -339,7 +365,7 @@ __global__ __launch_bounds__(kBlock) void recode_scatter_kernel(const Fr* __rest
         } else {
           lents[p] = make_entry(key, val);
         }
-      }, glen, gstep, fold_w, fold_n);
+      }, glen, gstep, fold_w, fold_n, narrow);
   }
   __syncthreads();
   const uint32_t total = loff[255] + cur[255];

@@ -48,6 +48,7 @@ class VariableBaseMSMGpu:
         self.curve = curve
         self.curve_id = CURVES[curve]
         self.window_bits = 0  # forced window bits (set_window_bits), 0 = the size's default
+        self.mixed_windows = 0  # windows of mixed widths (set_mixed_windows), 0 = off
         self.point_bytes, self.scalar_field = CURVE_INFO[curve]
         self.scalar_bytes = FIELD_BYTES[self.scalar_field]
         create, self._destroy, self._affine_msm = _CREATE[curve]
@@ -83,6 +84,12 @@ class VariableBaseMSMGpu:
         del keep
         return out.raw
 
+    def _plain_only(self, what: str):
+        """Mixed-width windows are for plain runs: asking for them and `what`
+        is an error (the library would abort, not fall back)."""
+        if self.mixed_windows:
+            raise ValueError(f"{what} refused: {self.mixed_windows} mixed-width windows are set (set_mixed_windows(0) first)")
+
     def run_sharded(self, comm, bases, scalars, n=None) -> bytes:
         """This rank's shard of an MSM over a library communicator
         (tachyon_amd.dist.LibComm): the local partial, the all-gather and the
@@ -100,6 +107,8 @@ class VariableBaseMSMGpu:
         partial, all-gather and group sum inside the library
         (tachyon_mi355x_msm_gpu_sharded_plan_affine); every rank returns the
         whole MSM (affine bytes)."""
+        if shard.window_groups > 1:
+            self._plain_only("a window-range shard")
         pb, ps, _, keep = self._args(bases, scalars, shard.count)
         out = ctypes.create_string_buffer(self.point_bytes)
         ok = lib().tachyon_mi355x_msm_gpu_sharded_plan_affine(self.curve_id, self._ctx, comm.handle,
@@ -114,6 +123,8 @@ class VariableBaseMSMGpu:
         tensor or device pointer) in one launch sequence: MSM g takes
         scalars[g length .. (g+1) length) (host or device; zero-padded);
         returns count affine results -- tachyon_mi355x_msm_gpu_batch_affine."""
+        if count > 1:
+            self._plain_only("run_batch")
         pb = d_bases if isinstance(d_bases, int) else d_bases.data_ptr()
         ps, sn, ks = _ptr(scalars)
         if sn < length * count * self.scalar_bytes:
@@ -132,6 +143,7 @@ class VariableBaseMSMGpu:
         """Fixed-base table for run_folded: `fold` x n affine points into the
         device buffer d_out, copy k = 2^(k c W / fold) P_i (device tensors or
         pointers) -- tachyon_mi355x_msm_gpu_fold_bases."""
+        self._plain_only("fold_bases")
         pb = d_bases if isinstance(d_bases, int) else d_bases.data_ptr()
         po = d_out if isinstance(d_out, int) else d_out.data_ptr()
         if not isinstance(d_out, int) and d_out.numel() * d_out.element_size() < fold * n * self.point_bytes:
@@ -142,6 +154,7 @@ class VariableBaseMSMGpu:
     def run_folded(self, d_folded, d_scalars, n: int, fold: int) -> bytes:
         """The MSM of n device scalars over a fold_bases table (same n, same
         window bits); affine bytes -- tachyon_mi355x_msm_gpu_folded_affine."""
+        self._plain_only("run_folded")
         pb = d_folded if isinstance(d_folded, int) else d_folded.data_ptr()
         ps = d_scalars if isinstance(d_scalars, int) else d_scalars.data_ptr()
         out = ctypes.create_string_buffer(self.point_bytes)
@@ -153,6 +166,7 @@ class VariableBaseMSMGpu:
         """The windows [w_begin, w_end) of the MSM only: sum_w 2^(c w) S_w
         (affine).  Ranges tiling [0, W) add up to run(); see
         dist.window_split_msm."""
+        self._plain_only("run_window_range")
         pb, ps, n, keep = self._args(bases, scalars, n)
         out = ctypes.create_string_buffer(self.point_bytes)
         lib().tachyon_mi355x_msm_gpu_window_range_affine(self.curve_id, self._ctx, pb, ps, n, w_begin, w_end, out)
@@ -172,8 +186,22 @@ class VariableBaseMSMGpu:
 
     def set_window_bits(self, c: int):
         """Force the window bits of later runs (0 = the size's default)."""
+        if c:
+            self._plain_only("set_window_bits")
         lib().tachyon_mi355x_msm_gpu_set_window_bits(self.curve_id, self._ctx, c)
         self.window_bits = c
+
+    def set_mixed_windows(self, windows: int):
+        """`windows` windows of two widths for later plain runs (0 = off): with
+        c_lo = (bits + 1) // windows, the top bits + 1 - windows * c_lo windows
+        are c_lo + 1 bits wide, bits + 1 in all, and the sort keys are bucket
+        indices (tachyon_mi355x_msm_gpu_set_mixed_windows).  Not together with
+        forced window bits, a batch, a fold or a window range: those raise."""
+        if windows and self.window_bits:
+            raise ValueError(f"mixed-width windows refused: window bits are forced to {self.window_bits}")
+        if not lib().tachyon_mi355x_msm_gpu_set_mixed_windows(self.curve_id, self._ctx, windows):
+            raise ValueError(f"{windows} mixed-width windows refused (widths of 2 to 26 bits, at most 24 key bits)")
+        self.mixed_windows = windows
 
     def set_profile(self, on: bool):
         lib().tachyon_mi355x_msm_gpu_set_profile(self.curve_id, self._ctx, 1 if on else 0)
@@ -210,7 +238,7 @@ class VariableBaseMSMGpu:
         b = lib().tachyon_mi355x_msm_gpu_last_schedule(self.curve_id, self._ctx)
         return {"fused_recode": bool(b & 1), "recode_fed_sort": bool(b & 2), "narrow_staging": bool(b & 4),
                 "acc29": bool(b & 8), "lane_pair": bool(b & 16), "acc28": bool(b & 32),
-                "chains_checked": bool(b & 64), "entries_staged": bool(b & 128)}
+                "chains_checked": bool(b & 64), "entries_staged": bool(b & 128), "mixed_windows": bool(b & 256)}
 
     def last_divisions(self) -> int:
         """Point chunks the last run was split into (device memory or host-upload pipeline)."""
@@ -243,7 +271,22 @@ def shard_plan(curve: str, n_total: int, world: int, rank: int) -> MsmShard:
     return s
 
 
+def mixed_layout(curve: str, windows: int):
+    """The layout of `windows` mixed-width windows over the curve's scalars
+    (tachyon_mi355x_msm_mixed_layout; no GPU): a dict of c_lo, n_wide, key_bits
+    and the windows + 1 bit_offsets / bucket_offsets, or None where refused."""
+    c_lo, n_wide, key_bits = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_uint()
+    boff, koff = (ctypes.c_uint * (windows + 1))(), (ctypes.c_uint * (windows + 1))()
+    if not lib().tachyon_mi355x_msm_mixed_layout(CURVES[curve], windows, ctypes.byref(c_lo), ctypes.byref(n_wide),
+                                                 ctypes.byref(key_bits), boff, koff):
+        return None
+    return {"c_lo": c_lo.value, "n_wide": n_wide.value, "key_bits": key_bits.value,
+            "bit_offsets": list(boff), "bucket_offsets": list(koff)}
+
+
 def plan(curve: str, n: int):
+    """(window bits, windows) of a plain n-point run's default plan; with
+    mixed widths the bits of the narrow windows."""
     c, w = ctypes.c_uint(), ctypes.c_uint()
     lib().tachyon_mi355x_msm_plan(CURVES[curve], n, ctypes.byref(c), ctypes.byref(w))
     return c.value, w.value

@@ -2,7 +2,10 @@
 """Window-size sweep for the MSM (device-resident BN254 G1 inputs).
 
   python tools/tune_msm.py --log-n 26 --c 16 18 20 21 22
-Prints per-phase device time (HIP events) for each window size.
+  python tools/tune_msm.py --log-n 26 --c 0 --mixed 0 12 13 14
+Prints per-phase device time (HIP events) for each window size; --mixed W
+sweeps W windows of two widths (set_mixed_windows; 0 = the size's default
+plan, which --variants 134217728 keeps uniform) beside the uniform --c.
 """
 import argparse
 import json
@@ -17,6 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, nargs="+", default=[26])
     ap.add_argument("--c", type=int, nargs="+", default=[0])
+    ap.add_argument("--mixed", type=int, nargs="+", default=[0])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--non-uniform", action="store_true")
     ap.add_argument("--variants", type=int, nargs="+", default=[0])
@@ -40,8 +44,14 @@ def main():
         torch.cuda.synchronize()
         m = M.VariableBaseMSMGpu(args.curve)
         ref = None
-        for c, var in [(c, v) for _ in range(args.rounds) for c in args.c for v in args.variants]:
+        # every uniform c (with the default layout), then every mixed W (no forced bits)
+        layouts = [(c, 0) for c in args.c] + [(0, w) for w in args.mixed if w]
+        for c, mixed, var in [(c, w, v) for _ in range(args.rounds) for c, w in layouts for v in args.variants]:
+            if m.mixed_windows != mixed:
+                m.set_mixed_windows(0)
             m.set_window_bits(c)
+            if mixed:
+                m.set_mixed_windows(mixed)
             m.set_variant(var)
             m.set_profile(True)
             res = m.run(d_b, d_s)
@@ -54,7 +64,12 @@ def main():
                 times.append(m.last_timings())
                 assert r == ref or (var & 64), "result changed"
             best = min(range(args.reps), key=lambda i: walls[i])
-            print(json.dumps({"curve": args.curve, "log_n": lg, "c": c or M.plan(args.curve, n)[0], "variant": var, "wall_ms": round(walls[best], 3),
+            W, is_mixed = m.plan_windows(n), m.last_schedule().get("mixed_windows", False)
+            c_def, w_def = M.plan(args.curve, n)
+            # the bits of the (narrow) windows; None where variant bit 27 leaves the size's default plan
+            c_run = c or (M.mixed_layout(args.curve, W)["c_lo"] if is_mixed else c_def if w_def == W else None)
+            print(json.dumps({"curve": args.curve, "log_n": lg, "c": c_run, "windows": W, "mixed": is_mixed,
+                              "variant": var, "wall_ms": round(walls[best], 3),
                               **{k: round(v, 3) for k, v in times[best].items()}}), flush=True)
         m.close()
 
