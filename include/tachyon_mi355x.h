@@ -920,8 +920,9 @@ TACHYON_C_EXPORT void tachyon_mi355x_msm_gpu_set_window_bits(int curve, void* ct
  * plan).  Only a plain run takes them: a batch, a fold or forced window bits
  * are refused while they are set (those entry points return 0), and a window
  * range aborts.  Returns 1, or 0 (nothing changed) for a layout whose widths
- * leave 2 .. 26 bits or whose bucket indices need more than 24 key bits, and
- * with window bits forced. */
+ * leave 2 .. 26 bits or whose bucket indices need more than 24 key bits, with
+ * window bits forced, and with one or two windows per sort group set
+ * (_set_variant bits 2-3 = 1 or 2; 3, all windows in one group, is accepted). */
 TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_set_mixed_windows(int curve, void* ctx, unsigned windows);
 /* The layout of `windows` mixed-width windows for the curve's scalar field (no
  * GPU needed): c_lo, the number of wide windows (the top ones), the sort-key
@@ -937,7 +938,9 @@ TACHYON_C_EXPORT void tachyon_mi355x_msm_gpu_set_profile(int curve, void* ctx, i
  * window plan where mixed widths are the size's default; bit 23: two-level window sums
  * for the G2 / BLS12-381 G1 / FIPS reductions, measured slower; bit 24: the
  * G2 window segment sums in two passes; bit 25: the limb-field G1
- * accumulations read their entries by 8-byte loads, not LDS-staged chunks). */
+ * accumulations read their entries by 8-byte loads, not LDS-staged chunks).
+ * Also 0 (nothing changed) for bits 2-3 = 1 or 2 (one or two windows per sort
+ * group) while _set_mixed_windows is in force: the next run would abort. */
 TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_set_variant(int curve, void* ctx, int variant);
 /* device ms of the last run with profiling on: h2d, recode, sort, prep (bounds +
  * chunk scan), acc (the bucket-accumulation kernel alone), reduce, total,

@@ -462,6 +462,13 @@ static unsigned uniform_windows(int curve, const void* ctx, size_t size) {
   }) GUARD_END
   return 0;
 }
+// set_variant bits 2-3 = 1 or 2: one or two windows per sort group -- not a
+// plain run, so refused together with mixed-width windows (3 = all windows in
+// one group, the plain run's own grouping, is not)
+static bool window_groups_set(int variant) {
+  const int g = (variant >> 2) & 3;
+  return g == 1 || g == 2;
+}
 void tachyon_mi355x_msm_gpu_affine(int curve, void* ctx, const void* bases, const void* scalars, size_t size,
                                    void* out_affine) {
   GUARD_BEGIN CURVE_DISPATCH(curve, msm_affine_out<C>(ctx, bases, scalars, size, out_affine)) GUARD_END
@@ -580,6 +587,7 @@ int tachyon_mi355x_msm_gpu_set_mixed_windows(int curve, void* ctx, unsigned wind
   CURVE_DISPATCH(curve, {
     auto* m = static_cast<MsmCtx<C>*>(ctx);
     if (windows && m->impl.force_window_bits()) return 0;  // not with forced window bits
+    if (windows && window_groups_set(m->impl.variant())) return 0;  // nor with one or two windows per sort group
     m->set([&](auto& g) { g.set_mixed_windows(windows); });
   })
   GUARD_END
@@ -642,7 +650,12 @@ void tachyon_mi355x_msm_gpu_set_profile(int curve, void* ctx, int on) {
 int tachyon_mi355x_msm_gpu_set_variant(int curve, void* ctx, int variant) {
   if (variant < 0 || (variant & ~msm::kMsmVariantMask)) return 0;  // unknown bits: refused, nothing changed
   GUARD_BEGIN
-  CURVE_DISPATCH(curve, static_cast<MsmCtx<C>*>(ctx)->set([&](auto& m) { m.set_variant(variant); }))
+  CURVE_DISPATCH(curve, {
+    auto* m = static_cast<MsmCtx<C>*>(ctx);
+    // window groups while mixed-width windows are set: the next run would throw (refused, nothing changed)
+    if (m->impl.mixed_windows() && window_groups_set(variant)) return 0;
+    m->set([&](auto& g) { g.set_variant(variant); });
+  })
   GUARD_END
   return 1;
 }

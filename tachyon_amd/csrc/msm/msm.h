@@ -433,6 +433,13 @@ class MsmGpu {
   };
   static SlotBytes slot_bytes(const AccFields& f, int variant);
   static bool window_sums_by_scan(const AccFields& f, unsigned buckets);  // no segment sums then
+  // Mixed widths: the running-sum segment length of a width class (`windows`
+  // windows of `buckets` buckets), and the segment sums seg_a_ / seg_b_ each
+  // hold for the two classes of a layout (`narrow` windows of B buckets, W -
+  // narrow of 2 B) -- the larger class's, a class that goes by the scan having
+  // none.  The one count window_sums allocates by and work_bytes estimates by.
+  static unsigned class_seg(unsigned windows, unsigned buckets);
+  static size_t mixed_seg_sums(const AccFields& f, unsigned narrow, unsigned W, unsigned B);
   // The sort of a run's entries (enqueue) and what its scratch takes
   // (work_bytes): the recode knobs of the variant bits (the recode fused with
   // the low-byte radix pass, bit 7 off; rocPRIM's digit histogram pass instead

@@ -837,20 +837,19 @@ template <class Curve>
 void MsmGpu<Curve>::window_sums(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows) {
   if (s.mixed) {
     const unsigned classes[2][3] = {{0, s.narrow, s.B}, {s.narrow, s.W - s.narrow, 2 * s.B}};  // first window, windows, B
-    // the segment sums of both classes share seg_a_ / seg_b_: sized for the larger before either is enqueued
-    size_t seg_sums = 0;
-    for (const auto& cl : classes) seg_sums = std::max(seg_sums, (size_t)cl[1] * (cl[2] / MsmPlan::seg_for(cl[1], cl[2])));
-    seg_a_.ensure(seg_sums * sizeof(Point));
-    seg_b_.ensure(seg_sums * sizeof(Point));
+    // the segment sums of both classes share seg_a_ / seg_b_: sized for the larger
+    // before either is enqueued (none where both classes go by the scan)
+    if (const size_t seg_sums = mixed_seg_sums(acc_, s.narrow, s.W, s.B)) {
+      seg_a_.ensure(seg_sums * sizeof(Point));
+      seg_b_.ensure(seg_sums * sizeof(Point));
+    }
     for (const auto& cl : classes) {
       if (cl[1] == 0) continue;
       Shape sc = s;
       Buffers bc = b;
       sc.mixed = false;
       sc.W = cl[1], sc.B = cl[2];
-      sc.seg = MsmPlan::seg_for(cl[1], cl[2]);
-      if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>)  // (as run_plan's G2 rule)
-        sc.seg = std::min(sc.B, std::min(128u, sc.seg * 2));
+      sc.seg = class_seg(cl[1], cl[2]);
       sc.seg_tree = MsmPlan::seg_tree_for(cl[1], cl[2]);
       bc.bucket_sum = reinterpret_cast<Point*>(reinterpret_cast<char*>(b.bucket_sum) +
                                                (size_t)cl[0] * s.B * s.sb.slot);
@@ -1095,6 +1094,25 @@ bool MsmGpu<Curve>::window_sums_by_scan(const AccFields& f, unsigned buckets) {
   return std::is_same_v<Curve, Bn254G1> && f.acc29 && !f.tree_reduce && buckets <= detail::kBlock;
 }
 
+// Mixed widths: a width class takes the segment length of its own window and
+// bucket counts (G2: twice the G1 rule's length, as run_plan's uniform rule)
+template <class Curve>
+unsigned MsmGpu<Curve>::class_seg(unsigned windows, unsigned buckets) {
+  unsigned seg = MsmPlan::seg_for(windows, buckets);
+  if constexpr (std::is_same_v<Curve, Bn254G2> || std::is_same_v<Curve, Bls381G2>)
+    seg = std::min(buckets, std::min(128u, seg * 2));
+  return seg;
+}
+
+template <class Curve>
+size_t MsmGpu<Curve>::mixed_seg_sums(const AccFields& f, unsigned narrow, unsigned W, unsigned B) {
+  const unsigned classes[2][2] = {{narrow, B}, {W - narrow, 2 * B}};  // windows, buckets per window
+  size_t sums = 0;
+  for (const auto& cl : classes)
+    if (cl[0] && !window_sums_by_scan(f, cl[1])) sums = std::max(sums, (size_t)cl[0] * (cl[1] / class_seg(cl[0], cl[1])));
+  return sums;
+}
+
 // The plan run_windows runs n points by: MsmPlan::make for the context's
 // window range, then the variant bits that change it.
 template <class Curve>
@@ -1249,8 +1267,10 @@ size_t MsmGpu<Curve>::work_bytes(size_t n, unsigned c, size_t batch) const {
   // (a batch of `batch` MSMs over n points in all keeps a block of windows per MSM)
   bytes += batch * p.total_buckets() * slot;                                // bucket sums
   // segment sums (x2), where the window sums are not one scan launch per window
-  // (mixed widths: at most this, the classes share them)
-  if (!window_sums_by_scan(acc_fields(variant_), p.buckets))
+  // (mixed widths: the two width classes share them, mixed_seg_sums)
+  if (p.mixed)
+    bytes += 2 * mixed_seg_sums(acc_fields(variant_), p.narrow(), p.windows, p.buckets) * sizeof(Point);
+  else if (!window_sums_by_scan(acc_fields(variant_), p.buckets))
     bytes += 2 * batch * p.active() * (p.buckets / p.seg) * sizeof(Point);
   return bytes + bytes / 10;
 }

@@ -41,6 +41,13 @@ def _ptr(x):
     raise TypeError(f"unsupported buffer type {type(x)}")
 
 
+def _window_groups(variant: int) -> int:
+    """Windows per sort group that set_variant bits 2-3 force (1 or 2), or 0:
+    the default and 3 (all windows in one group) are the plain run's grouping."""
+    g = (variant >> 2) & 3
+    return g if g in (1, 2) else 0
+
+
 class VariableBaseMSMGpu:
     def __init__(self, curve: str = "bn254_g1", degree: int = 0):
         if curve not in CURVES:
@@ -49,6 +56,7 @@ class VariableBaseMSMGpu:
         self.curve_id = CURVES[curve]
         self.window_bits = 0  # forced window bits (set_window_bits), 0 = the size's default
         self.mixed_windows = 0  # windows of mixed widths (set_mixed_windows), 0 = off
+        self.variant = 0  # set_variant bits, 0 = the default schedule
         self.point_bytes, self.scalar_field = CURVE_INFO[curve]
         self.scalar_bytes = FIELD_BYTES[self.scalar_field]
         create, self._destroy, self._affine_msm = _CREATE[curve]
@@ -196,9 +204,13 @@ class VariableBaseMSMGpu:
         c_lo = (bits + 1) // windows, the top bits + 1 - windows * c_lo windows
         are c_lo + 1 bits wide, bits + 1 in all, and the sort keys are bucket
         indices (tachyon_mi355x_msm_gpu_set_mixed_windows).  Not together with
-        forced window bits, a batch, a fold or a window range: those raise."""
+        forced window bits, window groups (set_variant(4) / (8)), a batch, a
+        fold or a window range: those raise."""
         if windows and self.window_bits:
             raise ValueError(f"mixed-width windows refused: window bits are forced to {self.window_bits}")
+        if windows and _window_groups(self.variant):
+            raise ValueError(f"mixed-width windows refused: variant {self.variant:#x} sets {_window_groups(self.variant)} "
+                             "window(s) per sort group (set_variant bits 2-3)")
         if not lib().tachyon_mi355x_msm_gpu_set_mixed_windows(self.curve_id, self._ctx, windows):
             raise ValueError(f"{windows} mixed-width windows refused (widths of 2 to 26 bits, at most 24 key bits)")
         self.mixed_windows = windows
@@ -207,8 +219,14 @@ class VariableBaseMSMGpu:
         lib().tachyon_mi355x_msm_gpu_set_profile(self.curve_id, self._ctx, 1 if on else 0)
 
     def set_variant(self, variant: int):
+        """Kernel-variant bits for A/B tuning (0 = the default schedule).  One
+        or two windows per sort group (bits 2-3 = 1 or 2) are not a plain run:
+        with mixed-width windows set they raise, and nothing changes."""
+        if variant >= 0 and _window_groups(variant):
+            self._plain_only(f"variant {variant:#x} ({_window_groups(variant)} window(s) per sort group, bits 2-3)")
         if not lib().tachyon_mi355x_msm_gpu_set_variant(self.curve_id, self._ctx, variant):
             raise ValueError(f"unknown MSM variant bits in {variant:#x}")
+        self.variant = variant
 
     def set_devices(self, device_ids):
         """Shard every later MSM over these devices (one point chunk per entry,

@@ -28,6 +28,7 @@ def test_msm_sweep_vs_oracle(logn):
     got = m.run(d_b, d_s)
     hb, hs = d_b.cpu().numpy(), d_s.cpu().numpy()
     del d_b, d_s
+    assert m.last_schedule()["mixed_windows"] == (logn == 26)
     m.close()
     assert O.msm_np("bn254_g1", hb, hs) == got
 

@@ -38,17 +38,19 @@ def expected_layout(bits, W):
 
 @pytest.mark.parametrize("curve", ["bn254_g1", "bls12_381_g1"])
 def test_mixed_plan_arithmetic(curve):
-    """The plan through the C entry point, W = 8 .. 64, for 254- and 255-bit
-    scalars: the widths add up to bits + 1, the bit and bucket offsets are the
-    running sums of the widths and of 2^(c_w - 1), the largest key is below the
-    reserved key 2^key_bits - 1, and a layout over 24 key bits is refused."""
+    """The plan through the C entry point, W = 8 .. bits + 1, for 254- and
+    255-bit scalars: the widths add up to bits + 1, the bit and bucket offsets
+    are the running sums of the widths and of 2^(c_w - 1), the largest key is
+    below the reserved key 2^key_bits - 1, and a layout over 24 key bits or
+    with windows of one bit (W over (bits + 1) / 2) is refused."""
     from tachyon_amd import msm as M
     bits = BITS[curve]
     seen_ok = seen_refused = 0
-    for W in range(8, 65):
+    for W in range(8, bits + 2):
         c_lo, n_wide, widths, total = expected_layout(bits, W)
         lay = M.mixed_layout(curve, W)
-        if total - 1 >= (1 << 24) - 1:  # the largest bucket index would reach the reserved 24-bit key
+        # the largest bucket index would reach the reserved 24-bit key, or the narrow windows have one bit
+        if total - 1 >= (1 << 24) - 1 or c_lo < 2:
             assert lay is None, (W, lay)
             seen_refused += 1
             continue
