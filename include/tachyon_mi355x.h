@@ -1323,6 +1323,182 @@ TACHYON_C_EXPORT size_t tachyon_mi355x_grand_product_tile_rows(void);
 TACHYON_C_EXPORT size_t tachyon_mi355x_grand_product_walk_tiles(void);
 TACHYON_C_EXPORT void tachyon_mi355x_grand_product_last_timings(float* out_ms);
 
+/* PLONK quotient: the vanishing argument's h(X) (zk/plonk/vanishing/
+ * circuit_polynomial_builder.h:199-245, the Scroll shape; vanishing_utils.h:
+ * 65-112, 167-196; vanishing_prover_impl.h:106-112) on device-resident
+ * polynomials.
+ *
+ * A graph is a flattened expression (graph_evaluator.h, calculation.h,
+ * value_source.h), serialised field by field.  A source's `kind` follows
+ * value_source.h: 0 Constant, 1 Intermediate, 2 Fixed, 3 Advice, 4 Instance,
+ * 5 Challenge, 6 Beta, 7 Gamma, 8 Theta, 9 Y, 10 PreviousValue; `index` is
+ * the constant, intermediate, column or challenge index and `rotation_index`
+ * (column kinds only) an index into the graph's `rotations`.  A calculation's
+ * `op` follows calculation.h: 0 Add, 1 Sub, 2 Mul (a, b), 3 Square, 4 Double,
+ * 5 Negate, 7 Store (a), 6 Horner: a is the initial value, b the factor and
+ * the parts are parts[parts_begin .. parts_begin + parts_count) of the graph:
+ * v = a; for each part: v = v b + part.  The result goes to intermediate
+ * `target`.  A graph's value on a row is its last calculation's target, and
+ * zero for a graph with no calculation.  A column read at rotation r is
+ * col[(row + r) mod n] (zk/base/rotation.h:45-51, scale 1).
+ *
+ * A term group is what one evaluator adds to the per-row accumulator of one
+ * circuit, in the reference's order:
+ *   0 gates        acc = graph(PreviousValue = acc)   (custom_gate_evaluator.h)
+ *   1 permutation  permutation_evaluator.h:25-108 over num_z = ceil(m /
+ *                  (cs_degree - 2)) products, m = num_perm_columns; nothing
+ *                  for m = 0
+ *   2 lookup       lookup/halo2/evaluator.h:66-128 with graph = the compressed
+ *                  (A + beta)(S + gamma) of the argument (PreviousValue = 0)
+ *   3 shuffle      shuffle/evaluator.h:71-119 with graph = the input's A +
+ *                  gamma and graph2 = the shuffle's S + gamma
+ * each term folded as acc = acc y + term.
+ *
+ * tachyon_mi355x_quotient_evaluate_part runs one group over caller-held
+ * evaluations on one size-n coset: every column (table columns, l_first,
+ * l_last, l_active_row, z, a_perm, s_perm, sigmas) is n evaluations, host or
+ * device, and acc (n elements, host or device) is read and written in place.
+ * For the permutation x_scale is delta_start times the coset's extended omega
+ * power (beta zeta w_ext^i) and omega the size-n generator: the label of
+ * column k on row j is x_scale omega^j delta^k.
+ *
+ * tachyon_mi355x_quotient_h_poly is the driver: every polynomial is given by
+ * its n coefficients (host or device).  With P = 2^(extended_k - k) parts
+ * (extended_k: the least e with 2^e >= n (cs_degree - 1)) it evaluates, for
+ * each part i, everything on the coset zeta w_ext^i <w> with one batched
+ * transform, runs the groups of every circuit in order (gates, permutation,
+ * lookups, shuffles; the accumulator carries from circuit to circuit),
+ * multiplies by 1 / (zeta^n w_ext^(n i) - 1) while it scatters the part to
+ * ext[j P + i], and after the last part transforms back from the coset
+ * zeta <w_ext>.  out (host or device) receives n (cs_degree - 1)
+ * coefficients, or all n P with full != 0.  w_ext is ext_gen (the extended
+ * domain's generator, of order exactly 2^extended_k; else the call returns 0
+ * with a message), or with ext_gen null the field's 2^extended_k root of the
+ * active generator set; the size-n generator is w_ext^P.
+ * Fixed-column and sigma cosets are recomputed for every part.
+ *
+ * Elements are 32-byte Montgomery values, canonical on output.  Constants,
+ * challenges, theta, beta, gamma, y, zeta, delta, ext_gen, omega and x_scale
+ * are host memory.  Inputs are never written.
+ *
+ * Both return 1, or 0 with nothing written and no GPU call made when: field
+ * is not 0 (bn254 Fr) or 2 (bls12-381 Fr); a needed pointer is null; n is not
+ * a power of two, n < 2 or n > 2^30; cs_degree < 3; extended_k exceeds the
+ * field's two-adicity (or 30); a kind or op is out of range; a constant,
+ * column, rotation, challenge or Horner-part index is out of range; a target
+ * is >= num_intermediates; an intermediate is read before the calculation
+ * that writes it; a permutation column is not of kind 2, 3 or 4 or names no
+ * column; num_z differs from ceil(m / (cs_degree - 2)); a group kind is above
+ * 3.  h_poly also returns 0, with a message and nothing written, for an
+ * ext_gen of another order and for a zeta with zeta^n w_ext^(n i) = 1 on some
+ * part (X^n - 1 has no inverse there).  A HIP failure or a failed allocation
+ * returns 0 with a message on stderr; the calls never abort.
+ *
+ * work_bytes: the device memory one h_poly call of this shape holds at its
+ * peak (one part's cosets, the extended buffer, the accumulator, the spill
+ * workspace, the program upload and the transform tables), before anything
+ * is allocated; 0 for a shape the call refuses.  held_bytes: what the last
+ * h_poly call did hold.  tile_rows: the rows one workgroup owns; fast_slots:
+ * the intermediates of a lowered program that live in LDS (more spill to a
+ * [slot][row] workspace).  last_timings: milliseconds (stream events) of the
+ * last call's transforms, gates, permutation, lookups, shuffles, scatter and
+ * final inverse transform (evaluate_part fills its own group's entry). */
+typedef struct {
+  uint32_t kind, index, rotation_index;
+} tachyon_mi355x_quotient_source;
+typedef struct {
+  uint32_t op;
+  tachyon_mi355x_quotient_source a, b;
+  uint32_t parts_begin, parts_count;
+  uint32_t target;
+} tachyon_mi355x_quotient_calc;
+typedef struct {
+  const tachyon_mi355x_quotient_calc* calcs;
+  size_t num_calcs;
+  const tachyon_mi355x_quotient_source* parts;
+  size_t num_parts;
+  const void* constants;
+  size_t num_constants;
+  const int32_t* rotations;
+  size_t num_rotations;
+  size_t num_intermediates;
+} tachyon_mi355x_quotient_graph;
+/* one circuit's columns and challenges (the evaluation table of a graph) */
+typedef struct {
+  const void* const* fixed;
+  size_t num_fixed;
+  const void* const* advice;
+  size_t num_advice;
+  const void* const* instance;
+  size_t num_instance;
+  const void* challenges;
+  size_t num_challenges;
+} tachyon_mi355x_quotient_table;
+typedef struct {
+  int field;
+  size_t n;
+  uint32_t cs_degree;
+  int32_t last_row; /* the permutation's -(blinding_factors + 1) rotation */
+  const void *theta, *beta, *gamma, *y;
+  const void *l_first, *l_last, *l_active_row;
+} tachyon_mi355x_quotient_params;
+typedef struct {
+  uint32_t kind;
+  const tachyon_mi355x_quotient_graph* graph;
+  const tachyon_mi355x_quotient_graph* graph2;
+  const void* const* z;
+  size_t num_z;
+  const void *a_perm, *s_perm;
+  const tachyon_mi355x_quotient_source* perm_columns;
+  size_t num_perm_columns;
+  const void* const* sigmas;
+  const void *x_scale, *omega, *delta;
+} tachyon_mi355x_quotient_group;
+/* what the circuits of one proof share */
+typedef struct {
+  const tachyon_mi355x_quotient_graph* gates; /* null: no gate group */
+  const tachyon_mi355x_quotient_source* perm_columns;
+  size_t num_perm_columns;
+  const void* const* sigmas;
+  const tachyon_mi355x_quotient_graph* lookups;
+  size_t num_lookups;
+  const tachyon_mi355x_quotient_graph* shuffles; /* 2 per shuffle: input, shuffle */
+  size_t num_shuffles;
+} tachyon_mi355x_quotient_system;
+typedef struct {
+  tachyon_mi355x_quotient_table table;
+  const void* const* perm_z;
+  size_t num_perm_z;
+  const void* const* lookup_z; /* num_lookups each */
+  const void* const* lookup_a_perm;
+  const void* const* lookup_s_perm;
+  const void* const* shuffle_z; /* num_shuffles */
+} tachyon_mi355x_quotient_circuit;
+TACHYON_C_EXPORT int tachyon_mi355x_quotient_evaluate_part(const tachyon_mi355x_quotient_params* params,
+                                                           const tachyon_mi355x_quotient_table* table,
+                                                           const tachyon_mi355x_quotient_group* group, void* acc);
+TACHYON_C_EXPORT int tachyon_mi355x_quotient_h_poly(const tachyon_mi355x_quotient_params* params,
+                                                    const tachyon_mi355x_quotient_system* system,
+                                                    const tachyon_mi355x_quotient_circuit* circuits,
+                                                    size_t num_circuits, const void* zeta, const void* delta,
+                                                    const void* ext_gen, int full, void* out);
+TACHYON_C_EXPORT size_t tachyon_mi355x_quotient_work_bytes(const tachyon_mi355x_quotient_params* params,
+                                                           const tachyon_mi355x_quotient_system* system,
+                                                           const tachyon_mi355x_quotient_circuit* circuits,
+                                                           size_t num_circuits);
+TACHYON_C_EXPORT size_t tachyon_mi355x_quotient_held_bytes(void);
+/* The lowered program of one term group, on the host alone (no GPU call; the
+ * arguments of evaluate_part, acc unused): out[0] its instructions, out[1]
+ * the field products among them (Mul and Square), out[2] the column elements
+ * it reads per row, out[3] the slots it needs (those beyond fast_slots
+ * spill).  Returns 0 for a group evaluate_part refuses. */
+TACHYON_C_EXPORT int tachyon_mi355x_quotient_program_stats(const tachyon_mi355x_quotient_params* params,
+                                                           const tachyon_mi355x_quotient_table* table,
+                                                           const tachyon_mi355x_quotient_group* group, size_t* out);
+TACHYON_C_EXPORT size_t tachyon_mi355x_quotient_tile_rows(void);
+TACHYON_C_EXPORT size_t tachyon_mi355x_quotient_fast_slots(void);
+TACHYON_C_EXPORT void tachyon_mi355x_quotient_last_timings(float* out_ms);
+
 /* delete a Jacobian returned by an *_msm / *_msm_gpu entry point (for callers
  * that cannot use C++ delete, e.g. ctypes). */
 TACHYON_C_EXPORT void tachyon_mi355x_jacobian_destroy(int curve, void* jacobian);

@@ -224,6 +224,15 @@ SIGNATURES = [
     ("tachyon_mi355x_grand_product_tile_rows", sz, []),
     ("tachyon_mi355x_grand_product_walk_tiles", sz, []),
     ("tachyon_mi355x_grand_product_last_timings", None, [fp]),
+    # PLONK quotient h(X): graph evaluator and driver
+    ("tachyon_mi355x_quotient_evaluate_part", i32, [vp, vp, vp, vp]),
+    ("tachyon_mi355x_quotient_h_poly", i32, [vp, vp, vp, sz, vp, vp, vp, i32, vp]),
+    ("tachyon_mi355x_quotient_work_bytes", sz, [vp, vp, vp, sz]),
+    ("tachyon_mi355x_quotient_held_bytes", sz, []),
+    ("tachyon_mi355x_quotient_program_stats", i32, [vp, vp, vp, ctypes.POINTER(ctypes.c_size_t)]),
+    ("tachyon_mi355x_quotient_tile_rows", sz, []),
+    ("tachyon_mi355x_quotient_fast_slots", sz, []),
+    ("tachyon_mi355x_quotient_last_timings", None, [fp]),
     # field-generic NTT domains
     ("tachyon_mi355x_ntt_domain_create", vp, [i32, sz]),
     ("tachyon_mi355x_ntt_domain_destroy", None, [vp]),

@@ -198,6 +198,12 @@ class NttGenDomain {
   const Fr& group_gen() const { return gen_; }
   hipStream_t stream() const { return stream_; }
   size_t table_bytes() const;  // stage tables + 29-bit tables + cached coset tables
+  size_t scratch_bytes() const { return scratch_.capacity() + io_.capacity(); }  // the passes' own buffers
+  // What table_bytes() can reach for a domain of order 2^log_order with every
+  // coset entry in use, and what scratch_bytes() reaches after run() on
+  // `batch` arrays of 2^log_m elements: for a caller's memory estimate
+  static size_t table_bytes_bound(uint32_t log_order);
+  static size_t scratch_bytes_bound(uint32_t log_m, size_t batch);
 
   // In place on `batch` consecutive device arrays of 2^log_m elements, on the
   // coset h<w_m> (Montgomery h; 1 = the plain sub-domain), enqueued on

@@ -639,6 +639,28 @@ size_t NttGenDomain<Fr>::table_bytes() const {
   return bytes;
 }
 
+template <class Fr>
+size_t NttGenDomain<Fr>::table_bytes_bound(uint32_t log_order) {
+  const size_t n = size_t(1) << log_order, floor = 256;  // a DeviceBuffer's least allocation
+  using Tw = typename NttTw<Fr>::type;
+  // build_twiddles: the pass kernel's entries, and the Montgomery ones beside Shoup entries; both directions
+  size_t bytes = 2 * (n * sizeof(Tw) + floor);
+  if constexpr (!std::is_same_v<Tw, Fr>) bytes += 2 * (n * sizeof(Fr) + floor);
+  if constexpr (std::is_same_v<Fr, Bn254Fr>)  // init: the 29-bit tables
+    bytes += 2 * (std::min<size_t>(n, size_t(1) << 20) * sizeof(fr29::TwMont29) + floor) +
+             2 * (std::min<size_t>(n, size_t(1) << 14) * sizeof(fr29::TwShoup29) + floor);
+  // coset_tables: lo and hi of both directions per cached entry
+  const size_t lo_max = size_t(1) << ((log_order + 1) / 2), hi_max = size_t(1) << (log_order / 2);
+  return bytes + kCosetCacheEntries * 2 * ((lo_max + hi_max) * sizeof(Fr) + 2 * floor);
+}
+
+template <class Fr>
+size_t NttGenDomain<Fr>::scratch_bytes_bound(uint32_t log_m, size_t batch) {
+  // run29 / run32: one scratch array per batch entry when the plan has more than one pass
+  const bool is29 = std::is_same_v<Fr, Bn254Fr> && log_m >= 1 && log_m <= 20;
+  return std::max<size_t>(256, (batch << log_m) * (is29 ? sizeof(fr29::F29) : sizeof(Fr)));
+}
+
 // The power tables of (log_m, h): the cached entry, or the least recently
 // used one rebuilt on the device.  An entry's buffers are allocated once, at
 // the sizes of the largest sub-domain, so a rebuild only enqueues two kernels
