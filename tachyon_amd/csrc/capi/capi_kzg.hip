@@ -101,12 +101,6 @@ int tachyon_mi355x_kzg_commit_batch(tachyon_mi355x_kzg* p, int lagrange, const v
 // primitives on their own, and the grouping alone (host code).
 namespace {
 
-struct OwnedStream {
-  hipStream_t s = nullptr;
-  OwnedStream() { TA_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ~OwnedStream() { (void)hipStreamDestroy(s); }
-};
-
 template <class Fr>
 int linear_combination(const void* const* polys, const size_t* lens, const void* coeffs, size_t count, const void* d,
                        void* out, size_t out_len) {
@@ -125,7 +119,7 @@ int linear_combination(const void* const* polys, const size_t* lens, const void*
   std::vector<const Fr*> dev;
   ops.stage(reinterpret_cast<const Fr* const*>(polys), lens, count, &dev);
   std::vector<typename kzg::PolyOps<Fr>::Term> terms(count);
-  bool in_place = kzg::PolyOps<Fr>::usable_in_place(out);
+  bool in_place = usable_in_place(out);
   for (size_t i = 0; i < count; ++i) {
     terms[i] = {dev[i], lens[i], static_cast<const Fr*>(coeffs)[i]};
     if (static_cast<const void*>(dev[i]) == out) in_place = false;
@@ -154,7 +148,7 @@ int divide_by_roots(const void* poly, size_t len, const void* roots, size_t nroo
   std::vector<const Fr*> dev;
   const Fr* src = static_cast<const Fr*>(poly);
   ops.stage(&src, &len, 1, &dev);
-  const bool in_place = kzg::PolyOps<Fr>::usable_in_place(out_quotient) && out_quotient != dev[0];
+  const bool in_place = usable_in_place(out_quotient) && out_quotient != dev[0];
   Fr* dst = in_place ? static_cast<Fr*>(out_quotient) : static_cast<Fr*>(result.ensure(std::max<size_t>(1, qlen) * sizeof(Fr)));
   Fr* d_rems = static_cast<Fr*>(rems.ensure(nroots * sizeof(Fr)));
   ops.divide_by_roots(dev[0], len, static_cast<const Fr*>(roots), nroots, dst, d_rems);

@@ -22,12 +22,6 @@ namespace {
 std::mutex g_timings_mutex;
 float g_last_ms[3] = {0.f, 0.f, 0.f};
 
-struct OwnedStream {
-  hipStream_t s = nullptr;
-  OwnedStream() { TA_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-  ~OwnedStream() { (void)hipStreamDestroy(s); }
-};
-
 template <class Fr>
 void run_chains(size_t n, size_t u, const void* omega, const void* delta, const tachyon_mi355x_gp_poly* polys,
                 const size_t* chain_lens, size_t num_chains, const void* blinds, void* const* out_z, void* out_last) {

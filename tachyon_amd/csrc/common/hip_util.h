@@ -1,13 +1,20 @@
-// Small HIP runtime helpers shared by the MSM and NTT drivers.
+// Small HIP runtime helpers shared by the drivers.
 // (The reference's thin runtime layer is tachyon/device/gpu/: gpuStream /
 // gpuMemPool aliases, GpuMemory RAII, GpuPointerGetAttributes.)
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "sections.h"
 
 namespace tachyon_amd {
 
@@ -90,5 +97,109 @@ inline void require_gpu() {
   if (e != hipSuccess || n == 0)
     throw std::runtime_error("tachyon_mi355x: no HIP device available (the MI355X backend has no CPU fallback)");
 }
+
+// True for a pointer the Fr kernels can use in place: device memory on a
+// 16-byte boundary (anything else is staged)
+inline bool usable_in_place(const void* p) { return is_device_pointer(p) && ((uintptr_t)p & 15) == 0; }
+
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() { TA_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  OwnedStream(const OwnedStream&) = delete;
+  OwnedStream& operator=(const OwnedStream&) = delete;
+  ~OwnedStream() { (void)hipStreamDestroy(s); }
+};
+
+// Runs f; if it throws, the stream is drained first, so that nothing of the
+// caller's stays in flight
+template <class Fn>
+void drained_on_throw(hipStream_t stream, Fn&& f) {
+  try {
+    f();
+  } catch (...) {
+    (void)hipStreamSynchronize(stream);
+    throw;
+  }
+}
+
+// Device views of `count` columns of lens[i] elements each: the pointer itself
+// where it is usable in place, else a copy in `buf`, enqueued on `stream` --
+// each distinct column once, so equal columns have equal views.  An empty
+// column's view is null.  The copies are valid until buf's next use.
+template <class T>
+std::vector<T*> stage_columns(T* const* ptrs, const size_t* lens, size_t count, DeviceBuffer& buf,
+                              hipStream_t stream) {
+  using Elem = std::remove_const_t<T>;
+  std::map<std::pair<T*, size_t>, T*> view;  // null: to be copied
+  size_t total = 0;
+  for (size_t i = 0; i < count; ++i) {
+    if (!lens[i]) continue;
+    const auto [it, fresh] = view.emplace(std::make_pair(ptrs[i], lens[i]), nullptr);
+    if (!fresh) continue;
+    if (usable_in_place(ptrs[i])) it->second = ptrs[i];
+    else total += lens[i];
+  }
+  Elem* d = total ? static_cast<Elem*>(buf.ensure(total * sizeof(Elem))) : nullptr;
+  std::vector<T*> dev(count, nullptr);
+  for (size_t i = 0; i < count; ++i) {
+    if (!lens[i]) continue;
+    T*& v = view[{ptrs[i], lens[i]}];
+    if (!v) {
+      TA_HIP(hipMemcpyAsync(d, ptrs[i], lens[i] * sizeof(Elem), hipMemcpyDefault, stream));
+      v = d;
+      d += lens[i];
+    }
+    dev[i] = v;
+  }
+  return dev;
+}
+
+// The packer's image into `buf`, enqueued on `stream` (the packer keeps the
+// host side alive); returns the device address
+inline unsigned char* upload_image(const SectionPacker& image, DeviceBuffer& buf, hipStream_t stream) {
+  const size_t bytes = image.size() ? image.size() : 1;
+  unsigned char* d = static_cast<unsigned char*>(buf.ensure(bytes));
+  TA_HIP(hipMemcpyAsync(d, image.data(), bytes, hipMemcpyHostToDevice, stream));
+  return d;
+}
+
+// Stream-event spans of one call, summed by phase
+class PhaseClock {
+ public:
+  explicit PhaseClock(hipStream_t stream) : stream_(stream) {}
+  PhaseClock(const PhaseClock&) = delete;
+  PhaseClock& operator=(const PhaseClock&) = delete;
+  ~PhaseClock() {
+    for (Span& s : spans_) {
+      if (s.a) (void)hipEventDestroy(s.a);
+      if (s.b) (void)hipEventDestroy(s.b);
+    }
+  }
+  void begin(int phase) {
+    spans_.push_back({phase, nullptr, nullptr});
+    TA_HIP(hipEventCreate(&spans_.back().a));
+    TA_HIP(hipEventRecord(spans_.back().a, stream_));
+  }
+  void end() {
+    TA_HIP(hipEventCreate(&spans_.back().b));
+    TA_HIP(hipEventRecord(spans_.back().b, stream_));
+  }
+  // ms[phase] += the phase's spans, for the phases < count; after the stream
+  // is synchronised
+  void sum(float* ms, int count) const {
+    for (const Span& s : spans_) {
+      float t = 0.f;
+      if (s.phase < count && s.a && s.b && hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) ms[s.phase] += t;
+    }
+  }
+
+ private:
+  struct Span {
+    int phase;
+    hipEvent_t a, b;
+  };
+  hipStream_t stream_;
+  std::vector<Span> spans_;
+};
 
 }  // namespace tachyon_amd

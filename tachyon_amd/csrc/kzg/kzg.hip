@@ -220,45 +220,6 @@ void Kzg<Curve>::copy_srs(bool lagrange, Aff* host_out) const {
 
 namespace {
 
-// Stream-event spans of the phases of one call (0 evaluate, 1 combine,
-// 2 divide, 3 commit), summed per phase when the call ends
-class PhaseTimer {
- public:
-  explicit PhaseTimer(hipStream_t stream) : stream_(stream) {}
-  ~PhaseTimer() {
-    for (auto& s : spans_) {
-      (void)hipEventDestroy(s.start);
-      (void)hipEventDestroy(s.stop);
-    }
-  }
-  void begin(int phase) {
-    Span s{phase, nullptr, nullptr};
-    TA_HIP(hipEventCreate(&s.start));
-    TA_HIP(hipEventCreate(&s.stop));
-    TA_HIP(hipEventRecord(s.start, stream_));
-    spans_.push_back(s);
-  }
-  void end() { TA_HIP(hipEventRecord(spans_.back().stop, stream_)); }
-  // after the stream has been synchronised
-  void finish(float* ms) {
-    for (int i = 0; i < 4; ++i) ms[i] = 0;
-    for (auto& s : spans_) {
-      float t = 0;
-      TA_HIP(hipEventSynchronize(s.stop));
-      TA_HIP(hipEventElapsedTime(&t, s.start, s.stop));
-      ms[s.phase] += t;
-    }
-  }
-
- private:
-  struct Span {
-    int phase;
-    hipEvent_t start, stop;
-  };
-  hipStream_t stream_;
-  std::vector<Span> spans_;
-};
-
 // Coefficients of the interpolant of (x_k, y_k), k < n, the x_k distinct
 // (math::LagrangeInterpolate): sum_k y_k prod_{i != k} (X - x_i) / (x_k - x_i)
 template <class Fr>
@@ -300,7 +261,7 @@ bool Kzg<Curve>::evaluate_batch(const Fr* const* polys, const size_t* lens, size
   for (size_t i = 0; i < m; ++i)
     if (idx[i] >= count) return false;
   if (!poly_) poly_ = std::make_unique<PolyOps<Fr>>(stream_);
-  PhaseTimer timer(stream_);
+  PhaseClock timer(stream_);
   std::vector<const Fr*> dev;
   poly_->stage(polys, lens, count, &dev);
   std::vector<typename PolyOps<Fr>::Pair> pairs(m);
@@ -309,7 +270,8 @@ bool Kzg<Curve>::evaluate_batch(const Fr* const* polys, const size_t* lens, size
   poly_->evaluate(pairs.data(), m, out);
   timer.end();
   poly_->synchronize();
-  timer.finish(open_ms_);
+  std::fill(open_ms_, open_ms_ + 4, 0.f);
+  timer.sum(open_ms_, 4);
   return true;
 }
 
@@ -336,7 +298,7 @@ bool Kzg<Curve>::create_opening_proof(int scheme, const Fr* const* polys, const 
   if (scheme == kzg_open::kShplonk && num_groups == 0) return false;
 
   if (!poly_) poly_ = std::make_unique<PolyOps<Fr>>(stream_);
-  PhaseTimer timer(stream_);
+  PhaseClock timer(stream_);
   std::vector<const Fr*> dev;
   poly_->stage(polys, lens, count, &dev);
   auto squeeze = [&] {
@@ -346,7 +308,8 @@ bool Kzg<Curve>::create_opening_proof(int scheme, const Fr* const* polys, const 
   };
   auto done = [&](bool ok) {
     poly_->synchronize();
-    timer.finish(open_ms_);
+    std::fill(open_ms_, open_ms_ + 4, 0.f);
+    timer.sum(open_ms_, 4);
     return ok;
   };
   auto commit_and_write = [&](const std::vector<const Fr*>& ptrs, const std::vector<size_t>& qlens) {

@@ -57,11 +57,9 @@ class PolyOps {
     Fr z;
   };
 
-  // True for a pointer the kernels can read in place
-  static bool usable_in_place(const void* p) { return is_device_pointer(p) && ((uintptr_t)p & 15) == 0; }
   // Device views of `count` polynomials: the pointer itself where it is
   // aligned device memory, else a copy in this object's staging buffer
-  // (valid until the next stage() call).
+  // (stage_columns; valid until the next stage() call).
   void stage(const Fr* const* ptrs, const size_t* lens, size_t count, std::vector<const Fr*>* dev);
 
   // out[k] = sum_i c_i P_i[k] - d [k == 0] for k < out_len, one launch: every

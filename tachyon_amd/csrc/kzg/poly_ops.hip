@@ -5,38 +5,13 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../field/fr_device.h"
+
 namespace tachyon_amd::kzg {
 
 namespace {
 
 constexpr unsigned kWaves = kPolyBlock / 64;
-
-// 32-byte elements move as two 16-byte accesses (Fr alone is 4-byte aligned,
-// which would make them eight dword accesses)
-template <class Fr>
-__device__ __forceinline__ Fr load_fr(const Fr* p) {
-  static_assert(sizeof(Fr) == 32, "poly_ops: 8-limb scalar fields");
-  const uint4 lo = reinterpret_cast<const uint4*>(p)[0];
-  const uint4 hi = reinterpret_cast<const uint4*>(p)[1];
-  Fr r;
-  r.v[0] = lo.x, r.v[1] = lo.y, r.v[2] = lo.z, r.v[3] = lo.w;
-  r.v[4] = hi.x, r.v[5] = hi.y, r.v[6] = hi.z, r.v[7] = hi.w;
-  return r;
-}
-
-template <class Fr>
-__device__ __forceinline__ void store_fr(Fr* p, const Fr& x) {
-  reinterpret_cast<uint4*>(p)[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-  reinterpret_cast<uint4*>(p)[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-}
-
-template <class Fr>
-__device__ __forceinline__ Fr shfl_down_fr(const Fr& x, unsigned d) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < Fr::N; ++i) r.v[i] = (uint32_t)__shfl_down((int)x.v[i], d, 64);
-  return r;
-}
 
 // The thread's kPolyChunk coefficients from `base` (zero past len) and their
 // Horner value h = sum_j a[j] z^j
@@ -198,21 +173,7 @@ void PolyOps<Fr>::synchronize() {
 
 template <class Fr>
 void PolyOps<Fr>::stage(const Fr* const* ptrs, const size_t* lens, size_t count, std::vector<const Fr*>* dev) {
-  dev->assign(count, nullptr);
-  size_t total = 0;
-  for (size_t i = 0; i < count; ++i)
-    if (lens[i] && !usable_in_place(ptrs[i])) total += lens[i];
-  Fr* d = total ? static_cast<Fr*>(stage_.ensure(total * sizeof(Fr))) : nullptr;
-  for (size_t i = 0; i < count; ++i) {
-    if (!lens[i]) continue;
-    if (usable_in_place(ptrs[i])) {
-      (*dev)[i] = ptrs[i];
-      continue;
-    }
-    TA_HIP(hipMemcpyAsync(d, ptrs[i], lens[i] * sizeof(Fr), hipMemcpyDefault, stream_));
-    (*dev)[i] = d;
-    d += lens[i];
-  }
+  *dev = stage_columns(ptrs, lens, count, stage_, stream_);
 }
 
 template <class Fr>

@@ -85,17 +85,19 @@ class GrandProduct {
   void run(size_t n, size_t u, const Fr& omega, const Fr& delta, const Poly* polys, const size_t* chain_lens,
            size_t num_chains, const Fr* blinds, Fr* const* out_z, Fr* out_last, float* ms);
 
-  // True for a pointer the kernels can use in place (else it is staged)
-  static bool usable(const void* p) { return is_device_pointer(p) && ((uintptr_t)p & 15) == 0; }
   hipStream_t stream() const { return stream_; }
 
  private:
-  void enqueue(size_t n, size_t u, const Fr& omega, const Fr& delta, const Poly* polys, const size_t* chain_lens,
-               size_t num_chains, const Fr* blinds, Fr* const* out_z, Fr* out_last, float* ms);
+  struct Call;
+  // run's four steps; copy_out synchronises the stream
+  void stage(Call& c, Fr* const* out_z);
+  void pack(Call& c, const Fr& omega, const Fr& delta, const Fr* blinds);
+  void launch(const Call& c, PhaseClock& clock);
+  void copy_out(const Call& c, Fr* const* out_z, Fr* out_last);
 
   hipStream_t stream_;
   DeviceBuffer stage_, meta_, prods_, result_;
-  std::vector<unsigned char> host_meta_;  // the host image of the upload in flight
+  SectionPacker upload_;  // the host image of the upload in flight
 };
 
 extern template class GrandProduct<Bn254Fr>;

@@ -4,71 +4,15 @@
 
 #include <algorithm>
 #include <cstring>
-#include <unordered_map>
+
+#include "../common/omega_table.h"
+#include "../field/fr_device.h"
 
 namespace tachyon_amd::plonk {
 
 namespace {
 
 constexpr unsigned kWaves = kGpBlock / 64;
-// omega^j = A[j % kGpBlock] B[(j / kGpBlock) % kTabB] C[j / (kGpBlock kTabB)]
-constexpr unsigned kTabB = 256;
-
-// 32-byte elements move as two 16-byte accesses
-template <class Fr>
-__device__ __forceinline__ Fr load_fr(const Fr* p) {
-  static_assert(sizeof(Fr) == 32, "grand_product: 8-limb scalar fields");
-  const uint4 lo = reinterpret_cast<const uint4*>(p)[0];
-  const uint4 hi = reinterpret_cast<const uint4*>(p)[1];
-  Fr r;
-  r.v[0] = lo.x, r.v[1] = lo.y, r.v[2] = lo.z, r.v[3] = lo.w;
-  r.v[4] = hi.x, r.v[5] = hi.y, r.v[6] = hi.z, r.v[7] = hi.w;
-  return r;
-}
-
-template <class Fr>
-__device__ __forceinline__ void store_fr(Fr* p, const Fr& x) {
-  reinterpret_cast<uint4*>(p)[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-  reinterpret_cast<uint4*>(p)[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-}
-
-template <class Fr>
-__device__ __forceinline__ Fr shfl_fr(const Fr& x, unsigned src) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < Fr::N; ++i) r.v[i] = (uint32_t)__shfl((int)x.v[i], (int)(src & 63), 64);
-  return r;
-}
-
-// Exclusive product scan over the workgroup in thread order (kReverse: from
-// the last thread down): returns the product of x over the threads before
-// this one, *total the product over all of them (the same in every thread).
-// lds: kWaves elements; the leading barrier lets the previous use drain.
-template <class Fr, bool kReverse>
-__device__ __forceinline__ Fr block_scan_mul(const Fr& x, Fr* lds, Fr* total) {
-  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned pos = kReverse ? 63 - lane : lane;
-  // Kogge-Stone over the wave: s = product over the positions <= pos
-  Fr s = x;
-  for (unsigned d = 1; d < 64; d <<= 1) {
-    const Fr t = shfl_fr(s, kReverse ? lane + d : lane - d);
-    const Fr m = s * t;
-    if (pos >= d) s = m;
-  }
-  Fr e = shfl_fr(s, kReverse ? lane + 1 : lane - 1);
-  if (pos == 0) e = Fr::one();
-  __syncthreads();
-  if (pos == 63) lds[wave] = s;
-  __syncthreads();
-  Fr before = Fr::one(), acc = Fr::one();
-  for (unsigned i = 0; i < kWaves; ++i) {
-    const unsigned w = kReverse ? kWaves - 1 - i : i;
-    if (w == wave) before = acc;
-    acc = acc * lds[w];
-  }
-  *total = acc;
-  return before * e;
-}
 
 template <class Fr>
 struct DevFactor {
@@ -156,12 +100,8 @@ __global__ __launch_bounds__(kGpBlock) void gp_ratio_kernel(const DevJob<Fr>* __
 #pragma unroll
   for (unsigned k = 0; k < kGpChunk; ++k) wrow[k] = num[k] = den[k] = Fr::one();
   if (job.has_label) {
-    const Fr wl = load_fr(wtab + threadIdx.x);
 #pragma unroll
-    for (unsigned k = 0; k < kGpChunk; ++k) {
-      const uint32_t slab = base / kGpBlock + k;  // the same in the whole workgroup
-      wrow[k] = wl * (load_fr(wtab + kGpBlock + slab % kTabB) * load_fr(wtab + kGpBlock + kTabB + slab / kTabB));
-    }
+    for (unsigned k = 0; k < kGpChunk; ++k) wrow[k] = omega_at<kGpBlock>(wtab, threadIdx.x, base / kGpBlock + k);
   }
   multiply_factors<Fr>(factors, job, base, u, wrow, num, den);
 
@@ -178,8 +118,8 @@ __global__ __launch_bounds__(kGpBlock) void gp_ratio_kernel(const DevJob<Fr>* __
     pre[k] = run;
   }
   Fr total, unused;
-  const Fr before = block_scan_mul<Fr, false>(run, lds, &total);
-  Fr after = block_scan_mul<Fr, true>(run, lds, &unused);  // then also this thread's den[k+1..]
+  const Fr before = block_scan_mul<Fr, kGpBlock, false>(run, lds, &total);
+  Fr after = block_scan_mul<Fr, kGpBlock, true>(run, lds, &unused);  // then also this thread's den[k+1..]
   Fr nprod = Fr::one();
 #pragma unroll
   for (int k = (int)kGpChunk - 1; k >= 0; --k) {
@@ -191,7 +131,7 @@ __global__ __launch_bounds__(kGpBlock) void gp_ratio_kernel(const DevJob<Fr>* __
     if (j < u) store_fr(job.z + j, q);
   }
   Fr ntotal;
-  block_scan_mul<Fr, false>(nprod, lds, &ntotal);
+  block_scan_mul<Fr, kGpBlock, false>(nprod, lds, &ntotal);
   if (threadIdx.x == 0) {
     store_fr(prods + blockIdx.x, ntotal);
     store_fr(dens + blockIdx.x, total);
@@ -228,7 +168,7 @@ __global__ __launch_bounds__(kGpBlock) void gp_carry_kernel(const uint32_t* __re
     const uint32_t i = i0 + threadIdx.x;
     const Fr x = i < count ? load_fr(prods + first + i) : Fr::one();
     Fr total;
-    const Fr e = block_scan_mul<Fr, false>(x, lds, &total);
+    const Fr e = block_scan_mul<Fr, kGpBlock, false>(x, lds, &total);
     if (i < count) store_fr(carries + first + i, carry * e);
     carry = carry * total;
   }
@@ -262,7 +202,7 @@ __global__ __launch_bounds__(kGpBlock) void gp_apply_kernel(const DevJob<Fr>* __
     p = p * r[k];
   }
   Fr total;
-  Fr acc = load_fr(carries + blockIdx.x) * block_scan_mul<Fr, false>(p, lds, &total);
+  Fr acc = load_fr(carries + blockIdx.x) * block_scan_mul<Fr, kGpBlock, false>(p, lds, &total);
 #pragma unroll
   for (unsigned k = 0; k < kGpChunk; ++k) {
     const uint32_t j = j0 + k;
@@ -272,171 +212,157 @@ __global__ __launch_bounds__(kGpBlock) void gp_apply_kernel(const DevJob<Fr>* __
   }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+template <class Poly, class Fn>
+void for_each_factor(const Poly& p, Fn&& fn) {
+  for (size_t k = 0; k < p.num_count; ++k) fn(p.num[k]);
+  for (size_t k = 0; k < p.den_count; ++k) fn(p.den[k]);
+}
 
 }  // namespace
+
+// One run: its shape, the device views of its columns and outputs, its upload
+template <class Fr>
+struct GrandProduct<Fr>::Call {
+  size_t n, u;
+  const Poly* polys;
+  const size_t* chain_lens;
+  size_t num_chains;
+  size_t num_polys = 0, num_factors = 0, tpj = 0, total_tiles = 0;
+  bool any_label = false;
+  std::vector<const Fr*> cols;  // per factor in the jobs' order: its values, then its table (kTable)
+  std::vector<Fr*> z;           // per job: its rows on the device
+  // the upload: [jobs | factors | chains | omega tables | blinds]
+  size_t off_fac = 0, off_chain = 0, off_tab = 0, off_blind = 0;
+  const unsigned char* d_meta = nullptr;
+};
 
 template <class Fr>
 void GrandProduct<Fr>::run(size_t n, size_t u, const Fr& omega, const Fr& delta, const Poly* polys,
                            const size_t* chain_lens, size_t num_chains, const Fr* blinds, Fr* const* out_z,
                            Fr* out_last, float* ms) {
-  if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+  float unread[3];
+  if (!ms) ms = unread;
+  ms[0] = ms[1] = ms[2] = 0.f;
   if (!num_chains) return;
-  try {
-    enqueue(n, u, omega, delta, polys, chain_lens, num_chains, blinds, out_z, out_last, ms);
-  } catch (...) {
-    (void)hipStreamSynchronize(stream_);  // nothing of the caller's stays in flight
-    throw;
-  }
+  Call c{n, u, polys, chain_lens, num_chains};
+  for (size_t i = 0; i < num_chains; ++i) c.num_polys += chain_lens[i];
+  c.tpj = ceil_div(n, kGpTile);
+  c.total_tiles = c.num_polys * c.tpj;
+  drained_on_throw(stream_, [&] {
+    if (c.total_tiles > kGpMaxTiles) throw std::runtime_error("grand product: too many tiles for one call");
+    stage(c, out_z);
+    pack(c, omega, delta, blinds);
+    PhaseClock clock(stream_);
+    launch(c, clock);
+    copy_out(c, out_z, out_last);
+    clock.sum(ms, 3);
+  });
+}
+
+// Device views of the input columns, each distinct column once; the outputs
+// in place where they are aligned device memory
+template <class Fr>
+void GrandProduct<Fr>::stage(Call& c, Fr* const* out_z) {
+  std::vector<const Fr*> cols;
+  for (size_t i = 0; i < c.num_polys; ++i)
+    for_each_factor(c.polys[i], [&](const Factor& f) {
+      cols.push_back(f.values);
+      if (f.kind == kTable) cols.push_back(f.table);
+      c.any_label |= f.kind == kLabel;
+      ++c.num_factors;
+    });
+  const std::vector<size_t> lens(cols.size(), c.n);
+  c.cols = stage_columns(cols.data(), lens.data(), cols.size(), stage_, stream_);
+  size_t held = 0;
+  for (size_t i = 0; i < c.num_polys; ++i) held += usable_in_place(out_z[i]) ? 0 : 1;
+  Fr* res = held ? static_cast<Fr*>(result_.ensure(held * c.n * sizeof(Fr))) : nullptr;
+  c.z.resize(c.num_polys);
+  for (size_t i = 0, k = 0; i < c.num_polys; ++i) c.z[i] = usable_in_place(out_z[i]) ? out_z[i] : res + c.n * k++;
 }
 
 template <class Fr>
-void GrandProduct<Fr>::enqueue(size_t n, size_t u, const Fr& omega, const Fr& delta, const Poly* polys,
-                               const size_t* chain_lens, size_t num_chains, const Fr* blinds, Fr* const* out_z,
-                               Fr* out_last, float* ms) {
-  size_t num_polys = 0;
-  for (size_t c = 0; c < num_chains; ++c) num_polys += chain_lens[c];
-  const size_t tpj = ceil_div(n, kGpTile), total_tiles = num_polys * tpj, nblind = n - u - 1;
-  if (total_tiles > kGpMaxTiles) throw std::runtime_error("grand product: too many tiles for one call");
-
-  // device views of the input columns: each distinct column once
-  std::unordered_map<const Fr*, const Fr*> dev;
-  auto note = [&](const Fr* p) {
-    if (!dev.count(p)) dev[p] = usable(p) ? p : nullptr;
-  };
-  size_t num_factors = 0;
-  bool any_label = false;
-  for (size_t i = 0; i < num_polys; ++i) {
-    for (int side = 0; side < 2; ++side) {
-      const Factor* f = side ? polys[i].den : polys[i].num;
-      const size_t cnt = side ? polys[i].den_count : polys[i].num_count;
-      num_factors += cnt;
-      for (size_t k = 0; k < cnt; ++k) {
-        note(f[k].values);
-        if (f[k].kind == kTable) note(f[k].table);
-        any_label |= f[k].kind == kLabel;
-      }
-    }
-  }
-  size_t staged = 0;
-  for (auto& kv : dev) staged += kv.second ? 0 : 1;
-  if (staged) {
-    Fr* d = static_cast<Fr*>(stage_.ensure(staged * n * sizeof(Fr)));
-    for (auto& kv : dev) {
-      if (kv.second) continue;
-      TA_HIP(hipMemcpyAsync(d, kv.first, n * sizeof(Fr), hipMemcpyDefault, stream_));
-      kv.second = d;
-      d += n;
-    }
-  }
-  // outputs: in place where they are aligned device memory
-  std::vector<Fr*> z(num_polys);
-  size_t held = 0;
-  for (size_t i = 0; i < num_polys; ++i) held += usable(out_z[i]) ? 0 : 1;
-  Fr* res = held ? static_cast<Fr*>(result_.ensure(held * n * sizeof(Fr))) : nullptr;
-  for (size_t i = 0, k = 0; i < num_polys; ++i) z[i] = usable(out_z[i]) ? out_z[i] : res + n * k++;
-
-  // one upload: [jobs | factors | chains | omega tables | blinds]
-  const size_t tab_c = any_label ? ceil_div(n, (size_t)kGpBlock * kTabB) : 0;
-  const size_t tab_len = any_label ? kGpBlock + kTabB + tab_c : 0;
-  const size_t off_fac = align16(num_polys * sizeof(DevJob<Fr>));
-  const size_t off_chain = align16(off_fac + num_factors * sizeof(DevFactor<Fr>));
-  const size_t off_tab = align16(off_chain + num_chains * 2 * sizeof(uint32_t));
-  const size_t off_blind = off_tab + tab_len * sizeof(Fr);
-  const size_t meta_bytes = off_blind + num_polys * nblind * sizeof(Fr);
-  std::vector<unsigned char>& meta = host_meta_;
-  meta.assign(meta_bytes ? meta_bytes : 1, 0);
-  unsigned char* d_meta = static_cast<unsigned char*>(meta_.ensure(meta.size()));
-  auto* h_jobs = reinterpret_cast<DevJob<Fr>*>(meta.data());
-  auto* h_fac = reinterpret_cast<DevFactor<Fr>*>(meta.data() + off_fac);
-  auto* h_chain = reinterpret_cast<uint32_t*>(meta.data() + off_chain);
-  Fr* h_tab = reinterpret_cast<Fr*>(meta.data() + off_tab);
+void GrandProduct<Fr>::pack(Call& c, const Fr& omega, const Fr& delta, const Fr* blinds) {
+  const size_t blind_bytes = c.num_polys * (c.n - c.u - 1) * sizeof(Fr);
+  upload_.reset();
+  upload_.add(c.num_polys * sizeof(DevJob<Fr>));
+  c.off_fac = upload_.add(c.num_factors * sizeof(DevFactor<Fr>));
+  c.off_chain = upload_.add(c.num_chains * 2 * sizeof(uint32_t));
+  c.off_tab = upload_.add(c.any_label ? omega_table_size(c.n, kGpBlock) * sizeof(Fr) : 0);
+  c.off_blind = upload_.add(blind_bytes);
+  unsigned char* meta = upload_.image();
+  auto* h_jobs = reinterpret_cast<DevJob<Fr>*>(meta);
+  auto* h_fac = reinterpret_cast<DevFactor<Fr>*>(meta + c.off_fac);
+  auto* h_chain = reinterpret_cast<uint32_t*>(meta + c.off_chain);
   uint32_t nf = 0;
-  for (size_t i = 0; i < num_polys; ++i) {
+  const Fr* const* col = c.cols.data();
+  for (size_t i = 0; i < c.num_polys; ++i) {
     DevJob<Fr>& job = h_jobs[i];
     job.begin = nf;
+    job.num_end = nf + (uint32_t)c.polys[i].num_count;
     job.has_label = 0;
-    job.z = z[i];
-    for (int side = 0; side < 2; ++side) {
-      const Factor* f = side ? polys[i].den : polys[i].num;
-      const size_t cnt = side ? polys[i].den_count : polys[i].num_count;
-      for (size_t k = 0; k < cnt; ++k, ++nf) {
-        DevFactor<Fr>& o = h_fac[nf];
-        o.v = dev[f[k].values];
-        o.t = f[k].kind == kTable ? dev[f[k].table] : nullptr;
-        o.m = f[k].m;
-        if (f[k].kind == kLabel) {
-          o.m = (o.m * delta.pow(&f[k].label, 1)).canonical();
-          job.has_label = 1;
-        }
-        o.c = f[k].c;
-        o.kind = f[k].kind;
-        o.pad = 0;
+    job.z = c.z[i];
+    for_each_factor(c.polys[i], [&](const Factor& f) {
+      DevFactor<Fr>& o = h_fac[nf++];
+      o.v = *col++;
+      o.t = f.kind == kTable ? *col++ : nullptr;
+      o.m = f.m;
+      if (f.kind == kLabel) {
+        o.m = (o.m * delta.pow(&f.label, 1)).canonical();
+        job.has_label = 1;
       }
-      if (!side) job.num_end = nf;
-    }
+      o.c = f.c;
+      o.kind = f.kind;
+      o.pad = 0;
+    });
     job.end = nf;
   }
-  for (size_t c = 0, first = 0; c < num_chains; first += chain_lens[c++]) {
-    h_chain[2 * c] = (uint32_t)(first * tpj);
-    h_chain[2 * c + 1] = (uint32_t)(chain_lens[c] * tpj);
+  for (size_t i = 0, first = 0; i < c.num_chains; first += c.chain_lens[i++]) {
+    h_chain[2 * i] = (uint32_t)(first * c.tpj);
+    h_chain[2 * i + 1] = (uint32_t)(c.chain_lens[i] * c.tpj);
   }
-  if (any_label) {
-    auto powers = [](Fr* out, size_t count, const Fr& step) {
-      out[0] = Fr::one();
-      for (size_t k = 1; k < count; ++k) out[k] = (out[k - 1] * step).canonical();
-      return (out[count - 1] * step).canonical();
-    };
-    const Fr wb = powers(h_tab, kGpBlock, omega);
-    const Fr wc = powers(h_tab + kGpBlock, kTabB, wb);
-    powers(h_tab + kGpBlock + kTabB, tab_c, wc);
-  }
-  if (num_polys * nblind) memcpy(meta.data() + off_blind, blinds, num_polys * nblind * sizeof(Fr));
-  TA_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, stream_));
+  if (c.any_label) omega_table_fill(reinterpret_cast<Fr*>(meta + c.off_tab), c.n, kGpBlock, omega);
+  if (blind_bytes) memcpy(meta + c.off_blind, blinds, blind_bytes);
+  c.d_meta = upload_image(upload_, meta_, stream_);
+}
 
-  // per tile [product of ratios | carry-in | 1 / product of denominators], then every chain's last value
-  Fr* prods = static_cast<Fr*>(prods_.ensure((3 * total_tiles + num_chains) * sizeof(Fr)));
-  Fr* carries = prods + total_tiles;
-  Fr* dens = carries + total_tiles;
-  Fr* last = dens + total_tiles;
-  const auto* d_jobs = reinterpret_cast<const DevJob<Fr>*>(d_meta);
-  const auto* d_fac = reinterpret_cast<const DevFactor<Fr>*>(d_meta + off_fac);
-  const auto* d_chain = reinterpret_cast<const uint32_t*>(d_meta + off_chain);
-  const Fr* d_tab = reinterpret_cast<const Fr*>(d_meta + off_tab);
-  const Fr* d_blind = reinterpret_cast<const Fr*>(d_meta + off_blind);
-
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  auto mark = [&](int i) {
-    if (!ms) return;
-    TA_HIP(hipEventCreate(&ev[i]));
-    TA_HIP(hipEventRecord(ev[i], stream_));
-  };
-  mark(0);
-  if (total_tiles) {
-    hipLaunchKernelGGL(gp_ratio_kernel<Fr>, dim3((unsigned)total_tiles), dim3(kGpBlock), 0, stream_, d_jobs, d_fac,
-                       d_tab, (uint32_t)u, (uint32_t)tpj, prods, dens);
-    hipLaunchKernelGGL(gp_invert_kernel<Fr>, dim3(ceil_div(total_tiles, 64)), dim3(64), 0, stream_, dens, prods,
-                       (uint32_t)total_tiles);
+// prods_: per tile [product of ratios | carry-in | 1 / product of denominators], then every chain's last value
+template <class Fr>
+void GrandProduct<Fr>::launch(const Call& c, PhaseClock& clock) {
+  const size_t tiles = c.total_tiles;
+  Fr* prods = static_cast<Fr*>(prods_.ensure((3 * tiles + c.num_chains) * sizeof(Fr)));
+  Fr* carries = prods + tiles;
+  Fr* dens = carries + tiles;
+  const auto* d_jobs = reinterpret_cast<const DevJob<Fr>*>(c.d_meta);
+  clock.begin(0);
+  if (tiles) {
+    hipLaunchKernelGGL(gp_ratio_kernel<Fr>, dim3((unsigned)tiles), dim3(kGpBlock), 0, stream_, d_jobs,
+                       reinterpret_cast<const DevFactor<Fr>*>(c.d_meta + c.off_fac),
+                       reinterpret_cast<const Fr*>(c.d_meta + c.off_tab), (uint32_t)c.u, (uint32_t)c.tpj, prods, dens);
+    hipLaunchKernelGGL(gp_invert_kernel<Fr>, dim3(ceil_div(tiles, 64)), dim3(64), 0, stream_, dens, prods,
+                       (uint32_t)tiles);
   }
-  mark(1);
-  hipLaunchKernelGGL(gp_carry_kernel<Fr>, dim3((unsigned)num_chains), dim3(kGpBlock), 0, stream_, d_chain, prods,
-                     carries, last);
-  mark(2);
-  if (total_tiles)
-    hipLaunchKernelGGL(gp_apply_kernel<Fr>, dim3((unsigned)total_tiles), dim3(kGpBlock), 0, stream_, d_jobs, carries,
-                       dens, d_blind, (uint32_t)n, (uint32_t)u, (uint32_t)tpj);
-  mark(3);
-  hipError_t err = hipGetLastError();
-  for (size_t i = 0; i < num_polys && err == hipSuccess; ++i)
-    if (z[i] != out_z[i]) err = hipMemcpyAsync(out_z[i], z[i], n * sizeof(Fr), hipMemcpyDefault, stream_);
-  if (out_last && err == hipSuccess)
-    err = hipMemcpyAsync(out_last, last, num_chains * sizeof(Fr), hipMemcpyDeviceToHost, stream_);
-  if (err == hipSuccess) err = hipStreamSynchronize(stream_);
-  if (ms && err == hipSuccess)
-    for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  TA_HIP(err);
+  clock.end();
+  clock.begin(1);
+  hipLaunchKernelGGL(gp_carry_kernel<Fr>, dim3((unsigned)c.num_chains), dim3(kGpBlock), 0, stream_,
+                     reinterpret_cast<const uint32_t*>(c.d_meta + c.off_chain), prods, carries, dens + tiles);
+  clock.end();
+  clock.begin(2);
+  if (tiles)
+    hipLaunchKernelGGL(gp_apply_kernel<Fr>, dim3((unsigned)tiles), dim3(kGpBlock), 0, stream_, d_jobs, carries, dens,
+                       reinterpret_cast<const Fr*>(c.d_meta + c.off_blind), (uint32_t)c.n, (uint32_t)c.u,
+                       (uint32_t)c.tpj);
+  clock.end();
+  TA_HIP(hipGetLastError());
+}
+
+template <class Fr>
+void GrandProduct<Fr>::copy_out(const Call& c, Fr* const* out_z, Fr* out_last) {
+  for (size_t i = 0; i < c.num_polys; ++i)
+    if (c.z[i] != out_z[i]) TA_HIP(hipMemcpyAsync(out_z[i], c.z[i], c.n * sizeof(Fr), hipMemcpyDefault, stream_));
+  if (out_last)
+    TA_HIP(hipMemcpyAsync(out_last, prods_.template as<Fr>() + 3 * c.total_tiles, c.num_chains * sizeof(Fr),
+                          hipMemcpyDeviceToHost, stream_));
+  TA_HIP(hipStreamSynchronize(stream_));
 }
 
 template class GrandProduct<Bn254Fr>;

@@ -62,12 +62,10 @@ class Quotient {
   // The device memory the last h_poly call held when it returned
   size_t held_bytes() const { return held_; }
 
-  static bool usable(const void* p) { return is_device_pointer(p) && ((uintptr_t)p & 15) == 0; }
-
  private:
   hipStream_t stream_;
   DeviceBuffer cosets_, ext_, acc_, spill_, meta_, stage_;
-  std::vector<unsigned char> host_meta_;  // the host image of the upload in flight
+  SectionPacker upload_;  // the host image of the upload in flight
   size_t held_ = 0;
 };
 

@@ -6,6 +6,8 @@
 #include <cstring>
 #include <unordered_map>
 
+#include "../common/omega_table.h"
+#include "../field/fr_device.h"
 #include "../ntt/ntt.h"
 
 namespace tachyon_amd::plonk {
@@ -13,26 +15,6 @@ namespace tachyon_amd::plonk {
 namespace qp = quotient_plan;
 
 namespace {
-
-// omega^row = A[row % kQBlock] B[(row / kQBlock) % kTabB] C[row / (kQBlock kTabB)]
-constexpr unsigned kTabB = 256;
-
-template <class Fr>
-__device__ __forceinline__ Fr load_fr(const Fr* p) {
-  static_assert(sizeof(Fr) == 32, "quotient: 8-limb scalar fields");
-  const uint4 lo = reinterpret_cast<const uint4*>(p)[0];
-  const uint4 hi = reinterpret_cast<const uint4*>(p)[1];
-  Fr r;
-  r.v[0] = lo.x, r.v[1] = lo.y, r.v[2] = lo.z, r.v[3] = lo.w;
-  r.v[4] = hi.x, r.v[5] = hi.y, r.v[6] = hi.z, r.v[7] = hi.w;
-  return r;
-}
-
-template <class Fr>
-__device__ __forceinline__ void store_fr(Fr* p, const Fr& x) {
-  reinterpret_cast<uint4*>(p)[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
-  reinterpret_cast<uint4*>(p)[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
-}
 
 // What a lane needs besides the program: the read-only tables are separate
 // __restrict__ kernel arguments, so that the compiler may fetch them by
@@ -53,14 +35,8 @@ __device__ __forceinline__ Fr read_operand(const EvalArgs<Fr>& a, const uint4* l
                                            uint32_t rot, uint32_t row, const Fr& acc, const Fr& xrow) {
   switch (kind) {
     case qp::kLConst: return a.consts[index];
-    case qp::kLSlot: {
-      const uint4 lo = lds[(index * 2) * kQBlock + threadIdx.x];
-      const uint4 hi = lds[(index * 2 + 1) * kQBlock + threadIdx.x];
-      Fr r;
-      r.v[0] = lo.x, r.v[1] = lo.y, r.v[2] = lo.z, r.v[3] = lo.w;
-      r.v[4] = hi.x, r.v[5] = hi.y, r.v[6] = hi.z, r.v[7] = hi.w;
-      return r;
-    }
+    case qp::kLSlot:
+      return unpack_fr<Fr>(lds[(index * 2) * kQBlock + threadIdx.x], lds[(index * 2 + 1) * kQBlock + threadIdx.x]);
     case qp::kLSpill: return load_fr(a.spill + (size_t)index * a.n + row);
     case qp::kLColumn: {
       uint32_t j = row + rot;  // rot < n <= 2^30
@@ -72,10 +48,7 @@ __device__ __forceinline__ Fr read_operand(const EvalArgs<Fr>& a, const uint4* l
       using GlobalU4 = const __attribute__((address_space(1))) U4;
       GlobalU4* p = (GlobalU4*)(uintptr_t)(a.cols[index] + j);
       const U4 lo = p[0], hi = p[1];
-      Fr r;
-      r.v[0] = lo.x, r.v[1] = lo.y, r.v[2] = lo.z, r.v[3] = lo.w;
-      r.v[4] = hi.x, r.v[5] = hi.y, r.v[6] = hi.z, r.v[7] = hi.w;
-      return r;
+      return unpack_fr<Fr>(lo, hi);
     }
     case qp::kLAcc: return acc;
     default: return xrow;
@@ -98,9 +71,7 @@ __global__ __launch_bounds__(kQBlock) void quotient_eval_kernel(
   const Fr acc = load_fr(acc_rows + row);
   Fr xrow = Fr::zero();
   if (uses_xrow) {
-    const Fr w = load_fr(wtab + threadIdx.x) *
-                 (load_fr(wtab + kQBlock + blockIdx.x % kTabB) * load_fr(wtab + kQBlock + kTabB + blockIdx.x / kTabB));
-    xrow = xscale * w;
+    xrow = xscale * omega_at<kQBlock>(wtab, threadIdx.x, blockIdx.x);
   }
   Fr out = Fr::zero();
   auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); };  // the same in every lane
@@ -123,8 +94,7 @@ __global__ __launch_bounds__(kQBlock) void quotient_eval_kernel(
     }
     const uint32_t dst_kind = uni(ins.dst_kind), dst = uni(ins.dst);
     if (dst_kind == qp::kLSlot) {
-      lds[(dst * 2) * kQBlock + threadIdx.x] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-      lds[(dst * 2 + 1) * kQBlock + threadIdx.x] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+      pack_fr(r, &lds[(dst * 2) * kQBlock + threadIdx.x], &lds[(dst * 2 + 1) * kQBlock + threadIdx.x]);
     } else if (dst_kind == qp::kLSpill) {
       if (active) store_fr(spill + (size_t)dst * n + row, r);
     } else {
@@ -143,8 +113,6 @@ __global__ __launch_bounds__(kQBlock) void quotient_scatter_kernel(const Fr* __r
   if (j >= n) return;
   store_fr(ext + (((size_t)j << log_parts) + part), (load_fr(acc + j) * inv).canonical());
 }
-
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // One term group, planned: its program, its constant table and the
 // polynomials (or evaluations) behind its column table
@@ -254,18 +222,16 @@ std::vector<GroupPlan<Fr>> plan_call(const qp::Params& p, const qp::System& s, c
 }
 
 // The upload of a call: every group's [code | constants | column pointers],
-// then the omega power tables.  Returns its size; fills the groups' offsets.
+// then the omega power tables.  Fills the groups' offsets; returns the tables'.
 template <class Fr>
-size_t layout(std::vector<GroupPlan<Fr>>& groups, size_t n, size_t* off_tab) {
-  size_t at = 0;
+size_t layout(SectionPacker& up, std::vector<GroupPlan<Fr>>& groups, size_t n) {
+  up.reset();
   for (GroupPlan<Fr>& g : groups) {
-    g.off_code = at;
-    g.off_consts = at = align16(at + g.prog.code.size() * sizeof(qp::LInstr));
-    g.off_cols = at = align16(at + g.consts.size() * sizeof(Fr));
-    at = align16(at + g.cols.size() * sizeof(void*));
+    g.off_code = up.add(g.prog.code.size() * sizeof(qp::LInstr));
+    g.off_consts = up.add(g.consts.size() * sizeof(Fr));
+    g.off_cols = up.add(g.cols.size() * sizeof(void*));
   }
-  *off_tab = at;
-  return at + (kQBlock + kTabB + ceil_div(n, (size_t)kQBlock * kTabB)) * sizeof(Fr);
+  return up.add(omega_table_size(n, kQBlock) * sizeof(Fr));
 }
 
 template <class Fr>
@@ -295,25 +261,22 @@ PolyList poly_list(const std::vector<GroupPlan<Fr>>& groups) {
   return l;
 }
 
-// The image of the upload; device(col): the device address of a group's column
+// Lays out, fills and enqueues the upload; device(col): the device address of
+// a group's column.  Returns the device image; *off_tab: the tables' offset.
 template <class Fr, class DeviceFn>
-void fill_meta(std::vector<unsigned char>& meta, const std::vector<GroupPlan<Fr>>& groups, size_t off_tab, size_t n,
-               const Fr& omega, DeviceFn&& device) {
+const unsigned char* upload_groups(SectionPacker& up, DeviceBuffer& buf, hipStream_t stream,
+                                   std::vector<GroupPlan<Fr>>& groups, size_t n, const Fr& omega, size_t* off_tab,
+                                   DeviceFn&& device) {
+  *off_tab = layout(up, groups, n);
+  unsigned char* meta = up.image();
   for (const GroupPlan<Fr>& g : groups) {
-    memcpy(meta.data() + g.off_code, g.prog.code.data(), g.prog.code.size() * sizeof(qp::LInstr));
-    memcpy(meta.data() + g.off_consts, g.consts.data(), g.consts.size() * sizeof(Fr));
-    auto* cols = reinterpret_cast<const Fr**>(meta.data() + g.off_cols);
+    memcpy(meta + g.off_code, g.prog.code.data(), g.prog.code.size() * sizeof(qp::LInstr));
+    memcpy(meta + g.off_consts, g.consts.data(), g.consts.size() * sizeof(Fr));
+    auto* cols = reinterpret_cast<const Fr**>(meta + g.off_cols);
     for (size_t i = 0; i < g.cols.size(); ++i) cols[i] = device(g.cols[i]);
   }
-  Fr* tab = reinterpret_cast<Fr*>(meta.data() + off_tab);
-  auto powers = [](Fr* out, size_t count, const Fr& step) {
-    out[0] = Fr::one();
-    for (size_t k = 1; k < count; ++k) out[k] = (out[k - 1] * step).canonical();
-    return (out[count - 1] * step).canonical();
-  };
-  const Fr wb = powers(tab, kQBlock, omega);
-  const Fr wc = powers(tab + kQBlock, kTabB, wb);
-  powers(tab + kQBlock + kTabB, ceil_div(n, (size_t)kQBlock * kTabB), wc);
+  omega_table_fill(reinterpret_cast<Fr*>(meta + *off_tab), n, kQBlock, omega);
+  return upload_image(up, buf, stream);
 }
 
 template <class Fr>
@@ -326,42 +289,6 @@ void launch_group(const GroupPlan<Fr>& g, const unsigned char* d_meta, size_t of
                      reinterpret_cast<const Fr*>(d_meta + off_tab), acc, spill, (uint32_t)g.prog.code.size(),
                      (uint32_t)n, (uint32_t)g.prog.uses_xrow, xscale);
 }
-
-// Stream-event spans summed by phase
-struct PhaseClock {
-  hipStream_t stream;
-  bool on;
-  struct Span {
-    int phase;
-    hipEvent_t a, b;
-  };
-  std::vector<Span> spans;
-  PhaseClock(hipStream_t s, bool enabled) : stream(s), on(enabled) {}
-  ~PhaseClock() {
-    for (Span& s : spans) {
-      if (s.a) (void)hipEventDestroy(s.a);
-      if (s.b) (void)hipEventDestroy(s.b);
-    }
-  }
-  void begin(int phase) {
-    if (!on) return;
-    spans.push_back({phase, nullptr, nullptr});
-    TA_HIP(hipEventCreate(&spans.back().a));
-    TA_HIP(hipEventRecord(spans.back().a, stream));
-  }
-  void end() {
-    if (!on) return;
-    TA_HIP(hipEventCreate(&spans.back().b));
-    TA_HIP(hipEventRecord(spans.back().b, stream));
-  }
-  // after the stream is synchronised
-  void sum(float* ms) const {
-    for (const Span& s : spans) {
-      float t = 0.f;
-      if (s.a && s.b && hipEventElapsedTime(&t, s.a, s.b) == hipSuccess) ms[s.phase] += t;
-    }
-  }
-};
 
 // evaluate_part's one group
 template <class Fr>
@@ -398,35 +325,21 @@ void Quotient<Fr>::evaluate_part(const qp::Params& params, const qp::Table& tabl
   std::vector<GroupPlan<Fr>> groups;
   groups.push_back(plan_part<Fr>(params, table, group, own));
   if (!has_work(groups[0])) return;
-  try {
-    // the columns that are not aligned device memory are staged, each once
+  drained_on_throw(stream_, [&] {
+    // what is not aligned device memory is staged: the columns each once, the accumulator apart from them
     PolyList list = poly_list(groups);
-    std::vector<const Fr*> dev(list.polys.size());
-    size_t staged = usable(acc) ? 0 : 1;
-    for (const void* p : list.polys) staged += usable(p) ? 0 : 1;
-    Fr* d = staged ? static_cast<Fr*>(stage_.ensure(staged * n * sizeof(Fr))) : nullptr;
-    Fr* d_acc = static_cast<Fr*>(acc);
-    if (!usable(acc)) {
-      d_acc = d;
-      d += n;
-      TA_HIP(hipMemcpyAsync(d_acc, acc, n * sizeof(Fr), hipMemcpyDefault, stream_));
-    }
-    for (size_t i = 0; i < list.polys.size(); ++i) {
-      dev[i] = static_cast<const Fr*>(list.polys[i]);
-      if (usable(list.polys[i])) continue;
-      TA_HIP(hipMemcpyAsync(d, list.polys[i], n * sizeof(Fr), hipMemcpyDefault, stream_));
-      dev[i] = d;
-      d += n;
-    }
-    size_t off_tab = 0;
-    host_meta_.assign(layout(groups, n, &off_tab), 0);
+    const std::vector<size_t> lens(list.polys.size(), n);
+    const auto dev = stage_columns(reinterpret_cast<const Fr* const*>(list.polys.data()), lens.data(), lens.size(),
+                                   stage_, stream_);
+    Fr* const host_acc = static_cast<Fr*>(acc);
+    Fr* d_acc = stage_columns(&host_acc, &n, 1, acc_, stream_)[0];
     const Fr omega = group.omega ? from_bytes<Fr>(group.omega) : Fr::one();
-    fill_meta(host_meta_, groups, off_tab, n, omega, [&](const void* p) { return dev[list.index[p]]; });
-    auto* d_meta = static_cast<unsigned char*>(meta_.ensure(host_meta_.size()));
-    TA_HIP(hipMemcpyAsync(d_meta, host_meta_.data(), host_meta_.size(), hipMemcpyHostToDevice, stream_));
+    size_t off_tab = 0;
+    const unsigned char* d_meta = upload_groups(upload_, meta_, stream_, groups, n, omega, &off_tab,
+                                                [&](const void* p) { return dev[list.index[p]]; });
     const size_t spills = spill_slots(groups);
     Fr* spill = spills ? static_cast<Fr*>(spill_.ensure(spills * n * sizeof(Fr))) : nullptr;
-    PhaseClock clock(stream_, true);
+    PhaseClock clock(stream_);
     clock.begin(groups[0].phase);
     launch_group(groups[0], d_meta, off_tab, d_acc, spill, n, group.x_scale ? from_bytes<Fr>(group.x_scale) : Fr::one(),
                  stream_);
@@ -434,11 +347,8 @@ void Quotient<Fr>::evaluate_part(const qp::Params& params, const qp::Table& tabl
     TA_HIP(hipGetLastError());
     if (d_acc != acc) TA_HIP(hipMemcpyAsync(acc, d_acc, n * sizeof(Fr), hipMemcpyDefault, stream_));
     TA_HIP(hipStreamSynchronize(stream_));
-    clock.sum(ms);
-  } catch (...) {
-    (void)hipStreamSynchronize(stream_);  // nothing of the caller's stays in flight
-    throw;
-  }
+    clock.sum(ms, kQPhases);
+  });
 }
 
 template <class Fr>
@@ -450,8 +360,9 @@ size_t Quotient<Fr>::work_bytes(const qp::Params& params, const qp::System& syst
   const size_t n = params.n, polys = poly_list(groups).polys.size();
   const uint32_t log_ext = qp::extended_log(n, params.cs_degree);
   const size_t N = size_t(1) << log_ext;
-  size_t off_tab = 0;
-  const size_t meta = layout(groups, n, &off_tab);
+  SectionPacker up;
+  layout(up, groups, n);
+  const size_t meta = up.size();
   // cosets, the domain's scratch for the larger of the two transforms and its
   // tables (the domain's own bounds), ext, the accumulator, the spill rows
   using Dom = ntt::NttGenDomain<Fr>;
@@ -495,22 +406,20 @@ void Quotient<Fr>::h_poly(const qp::Params& params, const qp::System& system, co
   if (!dom.init(w_ext) || dom.log_order() != (int)log_ext)
     throw std::runtime_error("quotient: the extended generator's order is not 2^extended_k");
 
-  try {
+  drained_on_throw(stream_, [&] {
     Fr* cosets = static_cast<Fr*>(cosets_.ensure(std::max<size_t>(1, polys) * n * sizeof(Fr)));
     Fr* ext = static_cast<Fr*>(ext_.ensure(N * sizeof(Fr)));
     Fr* acc = static_cast<Fr*>(acc_.ensure(n * sizeof(Fr)));
     const size_t spills = spill_slots(groups);
     Fr* spill = spills ? static_cast<Fr*>(spill_.ensure(spills * n * sizeof(Fr))) : nullptr;
     size_t off_tab = 0;
-    host_meta_.assign(layout(groups, n, &off_tab), 0);
-    fill_meta(host_meta_, groups, off_tab, n, omega, [&](const void* p) { return cosets + list.index[p] * n; });
-    auto* d_meta = static_cast<unsigned char*>(meta_.ensure(host_meta_.size()));
-    TA_HIP(hipMemcpyAsync(d_meta, host_meta_.data(), host_meta_.size(), hipMemcpyHostToDevice, stream_));
+    const unsigned char* d_meta = upload_groups(upload_, meta_, stream_, groups, n, omega, &off_tab,
+                                                [&](const void* p) { return cosets + list.index[p] * n; });
 
     // per part: the coset zeta w_ext^i and the label scale delta_start w_ext^i
     const Fr beta = from_bytes<Fr>(params.beta);
     Fr cur = zeta.canonical();
-    PhaseClock clock(stream_, true);
+    PhaseClock clock(stream_);
     constexpr size_t kMaxBatch = 65535;  // of one transform call
     for (size_t i = 0; i < parts; ++i) {
       clock.begin(0);
@@ -539,13 +448,10 @@ void Quotient<Fr>::h_poly(const qp::Params& params, const qp::System& system, co
     const size_t count = full ? N : n * (size_t)(params.cs_degree - 1);
     TA_HIP(hipMemcpyAsync(out, ext, count * sizeof(Fr), hipMemcpyDefault, stream_));
     TA_HIP(hipStreamSynchronize(stream_));
-    clock.sum(ms);
+    clock.sum(ms, kQPhases);
     held_ = cosets_.capacity() + ext_.capacity() + acc_.capacity() + spill_.capacity() + meta_.capacity() +
             stage_.capacity() + dom.table_bytes() + dom.scratch_bytes();
-  } catch (...) {
-    (void)hipStreamSynchronize(stream_);
-    throw;
-  }
+  });
 }
 
 template class Quotient<Bn254Fr>;

@@ -78,24 +78,41 @@ def _is_cuda(x):
     return getattr(x, "is_cuda", False)
 
 
-def _column(x, n, keep, seen):
-    """Pointer of one column; an object passed twice is one buffer (one upload)."""
-    if id(x) not in seen:
-        p, nb, k = _ptr(x)
-        if nb != 32 * n:
-            raise ValueError("a column is n 32-byte elements")
-        keep.append(k)
-        seen[id(x)] = p
-    return seen[id(x)]
+class _Columns:
+    """The column arguments of one call: a pointer per object (an object passed
+    twice is one buffer, one upload), what keeps the buffers alive, and
+    whether anything is on the device."""
+
+    def __init__(self, n, error="a column is n 32-byte elements"):
+        self.n, self.error, self.keep, self.seen, self.cuda = n, error, [], {}, False
+
+    def ptr(self, x):
+        if id(x) not in self.seen:
+            p, nb, k = _ptr(x)
+            if nb != 32 * self.n:
+                raise ValueError(self.error)
+            self.hold(k)
+            self.seen[id(x)] = p
+        return self.seen[id(x)]
+
+    def hold(self, k):
+        self.keep.append(k)
+        self.cuda |= _is_cuda(k)
+
+    def sync(self):
+        if self.cuda:
+            # the library works on a stream of its own: what produced the tensors is done first
+            import torch
+            torch.cuda.current_stream().synchronize()
 
 
-def _fill(dst: GpFactor, f, n, keep, seen):
+def _fill(dst: GpFactor, f, cols):
     zero = b"\0" * 32
-    dst.values = _column(f["values"], n, keep, seen)
+    dst.values = cols.ptr(f["values"])
     dst.table = None
     dst.kind, dst.label = 0, 0
     if f.get("table") is not None:
-        dst.table, dst.kind = _column(f["table"], n, keep, seen), 1
+        dst.table, dst.kind = cols.ptr(f["table"]), 1
     elif f.get("label") is not None:
         dst.kind, dst.label = 2, int(f["label"])
     m = f.get("m")
@@ -116,13 +133,13 @@ def grand_product_chains(field, n, usable_rows, chains, omega, delta, blinds, ou
     per job Z as bytes (or the `out` tensor), per chain the final
     z[usable_rows] as bytes; None on a refusal."""
     jobs = [job for chain in chains for job in chain]
-    keep, seen, polys = [], {}, (GpPoly * max(1, len(jobs)))()
+    cols, polys = _Columns(n), (GpPoly * max(1, len(jobs)))()
     for i, (num, den) in enumerate(jobs):
         for side, lst in (("num", num), ("den", den)):
             arr = (GpFactor * max(1, len(lst)))()
             for k, f in enumerate(lst):
-                _fill(arr[k], f, n, keep, seen)
-            keep.append(arr)
+                _fill(arr[k], f, cols)
+            cols.hold(arr)
             setattr(polys[i], side, arr)
             setattr(polys[i], side + "_count", len(lst))
     lens = (ctypes.c_size_t * max(1, len(chains)))(*[len(c) for c in chains])
@@ -143,18 +160,15 @@ def grand_product_chains(field, n, usable_rows, chains, omega, delta, blinds, ou
             if nb != 32 * n:
                 raise ValueError("out: 32 n bytes per job")
             ptrs.append(p)
-            keep.append(k)
+            cols.hold(k)
     outs = (ctypes.c_void_p * max(1, len(jobs)))(*ptrs)
     last = ctypes.create_string_buffer(max(1, 32 * len(chains)))
     wbuf = ctypes.create_string_buffer(bytes(omega), 32) if omega is not None else None
     dbuf = ctypes.create_string_buffer(bytes(delta), 32) if delta is not None else None
-    if any(_is_cuda(k) for k in keep):
-        # the library works on a stream of its own: what produced the tensors is done first
-        import torch
-        torch.cuda.current_stream().synchronize()
+    cols.sync()
     ok = lib().tachyon_mi355x_grand_product_chains(FIELDS[field], n, usable_rows, wbuf, dbuf, polys, lens, len(chains),
                                                    blbuf, outs, last)
-    del keep
+    del cols
     if not ok:
         return None
     z = list(out) if out is not None else [b.raw[:32 * n] for b in bufs]

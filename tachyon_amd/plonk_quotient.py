@@ -19,7 +19,7 @@ import ctypes
 from . import params as P
 from ._lib import lib
 from .msm import _ptr
-from .plonk import FIELDS, _is_cuda, _mont
+from .plonk import FIELDS, _Columns, _is_cuda, _mont
 
 # value_source.h's kinds and calculation.h's ops, in their order
 CONSTANT, INTERMEDIATE, FIXED, ADVICE, INSTANCE, CHALLENGE, BETA, GAMMA, THETA, Y, PREVIOUS_VALUE = range(11)
@@ -286,23 +286,15 @@ class GraphEvaluator:
         dst.num_intermediates = len(self.calculations)
 
 
-class _Args:
+class _Args(_Columns):
     """The ctypes images of a call and what keeps them alive."""
 
     def __init__(self, field, n):
-        self.field, self.n, self.keep, self.seen, self.cuda = field, n, [], {}, False
+        super().__init__(n, "a column or polynomial is n 32-byte elements")
+        self.field = field
 
     def column(self, x):
-        if x is None:
-            return None
-        if id(x) not in self.seen:
-            p, nb, k = _ptr(x)
-            if nb != 32 * self.n:
-                raise ValueError("a column or polynomial is n 32-byte elements")
-            self.keep.append(k)
-            self.cuda |= _is_cuda(x)
-            self.seen[id(x)] = p
-        return self.seen[id(x)]
+        return None if x is None else self.ptr(x)
 
     def columns(self, xs):
         arr = (ctypes.c_void_p * max(1, len(xs)))(*[self.column(x) for x in xs])
@@ -354,12 +346,6 @@ class _Args:
         self.keep.append(arr)
         return arr
 
-    def sync(self):
-        if self.cuda:
-            # the library works on a stream of its own: what produced the tensors is done first
-            import torch
-            torch.cuda.current_stream().synchronize()
-
 
 def _part_args(field, n, kind, cs_degree, last_row, theta, beta, gamma, y, fixed, advice, instance, challenges, l_first,
                l_last, l_active_row, graph, graph2, z, a_perm, s_perm, perm_columns, sigmas, x_scale, omega, delta):
@@ -393,8 +379,7 @@ def quotient_evaluate_part(field, n, kind, acc, *, cs_degree=3, last_row=0, thet
                             sigmas, x_scale, omega, delta)
     if _is_cuda(acc):
         ptr, nb, k = _ptr(acc)
-        a.keep.append(k)
-        a.cuda = True
+        a.hold(k)
         buf = None
     else:
         buf = ctypes.create_string_buffer(bytes(acc), max(1, 32 * n))
@@ -490,8 +475,7 @@ def quotient_h_poly(field, n, circuits, *, cs_degree, last_row=0, theta, beta, g
         ptr, nb, k = _ptr(out)
         if nb != 32 * count:
             raise ValueError("out: 32 bytes per coefficient")
-        a.keep.append(k)
-        a.cuda = True
+        a.hold(k)
     a.sync()
     ok = lib().tachyon_mi355x_quotient_h_poly(ctypes.byref(p), ctypes.byref(s), c, len(circuits), a.elem(zeta),
                                               a.elem(delta), a.elem(ext_gen), 1 if full else 0, ptr)

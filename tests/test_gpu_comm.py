@@ -27,7 +27,7 @@ import torch.distributed as dist  # noqa: E402
 
 import torch.multiprocessing as mp  # noqa: E402
 
-from test_gpu_dist import _free_port, _run  # noqa: E402  (spawned gloo ranks on the one GPU)
+from test_gpu_dist import _run  # noqa: E402  (spawned gloo ranks on the one GPU)
 
 
 def _g16_inputs(curve="bn254", log_n=7):

@@ -10,7 +10,8 @@ one GPU of the box (the 8-GPU RCCL runs are the driver's).
   the oracle's FFT of the global vector; the inverse returns the input.
 """
 import os
-import socket
+import queue
+import time
 
 import pytest
 
@@ -21,25 +22,37 @@ import torch.distributed as dist  # noqa: E402
 import torch.multiprocessing as mp  # noqa: E402
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run(target, world, *args, timeout=240):
+    """target(rank, world, port, queue, *args) in `world` spawned processes; their
+    queue entries by rank.  This process holds the rendezvous store, on a port
+    the system hands out as the store binds (a port looked up first and bound
+    by rank 0 later can be taken in between), and every rank joins it as a
+    client: torchrun's arrangement.  A rank that dies ends the wait, and no
+    rank outlives the call."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=target, args=(r, world, port, q) + args) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=timeout) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    store = dist.TCPStore("127.0.0.1", 0, is_master=True, wait_for_workers=False)
+    procs = [ctx.Process(target=target, args=(r, world, store.port, q) + args) for r in range(world)]
+    os.environ["TORCHELASTIC_USE_AGENT_STORE"] = "True"  # the spawned ranks inherit it
+    try:
+        for p in procs:
+            p.start()
+        got, deadline = [], time.monotonic() + timeout
+        while len(got) < world:
+            try:
+                got.append(q.get(timeout=1))
+            except queue.Empty:
+                assert all(p.exitcode in (None, 0) for p in procs), [p.exitcode for p in procs]
+                assert time.monotonic() < deadline, "no result from every rank in time"
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0
+    finally:
+        del os.environ["TORCHELASTIC_USE_AGENT_STORE"]
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join()
     return sorted(got, key=lambda t: t[0])
 
 

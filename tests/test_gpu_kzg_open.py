@@ -189,6 +189,38 @@ def test_linear_combination(curve, count):
     assert poly_linear_combination(curve, mixed, cb) == raw(R.linear_combination([ints(p) for p in polys], coeffs, 0, F.p))
 
 
+def cuda_off_by_4(b):
+    """A CUDA tensor holding b that starts 4 bytes past a 16-byte boundary."""
+    import torch
+    view = torch.empty(len(b) + 16, dtype=torch.uint8, device="cuda")[4:4 + len(b)]
+    view.copy_(torch.frombuffer(bytearray(b), dtype=torch.uint8))
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
+@pytest.mark.parametrize("n", [3, 257])
+def test_staged_inputs_and_output(n):
+    """What the kernels cannot use in place is staged: one host array passed
+    twice, a device polynomial and a device output that are not 16-byte
+    aligned; 257 is one past a workgroup's threads."""
+    from tachyon_amd.kzg import poly_divide_by_roots, poly_linear_combination
+    F = pyref.Field("bn254_fr")
+    rng = random.Random(n)
+    a, b = rand_poly(F.name, 120, n), rand_poly(F.name, 121, n)
+    twice, unaligned = np.frombuffer(a, np.uint8), cuda_off_by_4(b)
+    coeffs = [rng.randrange(F.p) for _ in range(3)]
+    d = rng.randrange(F.p)
+    want = raw(R.linear_combination([ints(a), ints(a), ints(b)], coeffs, int.from_bytes(F.to_bytes(d), "little"), F.p))
+    out = cuda_off_by_4(bytes(32 * n))
+    got = poly_linear_combination("bn254_g1", [twice, twice, unaligned], [F.to_bytes(c) for c in coeffs], F.to_bytes(d),
+                                  out=out)
+    assert got is out and out.cpu().numpy().tobytes() == want
+    z = rng.randrange(F.p)
+    q, rems = poly_divide_by_roots("bn254_g1", unaligned, [F.to_bytes(z)])
+    want_q, want_r = R.divide_by_roots(ints(b), [z], F.p)
+    assert q == raw(want_q) and rems == [raw(want_r)]
+
+
 # --- evaluation -----------------------------------------------------------------------
 @pytest.mark.parametrize("curve", ["bn254_g1", "bls12_381_g1"])
 def test_evaluate_batch(curve):

@@ -173,6 +173,41 @@ def test_empty_graph_is_zero():
     assert cu == got
 
 
+def cuda_off_by_4(b):
+    """A CUDA tensor holding b that starts 4 bytes past a 16-byte boundary."""
+    import torch
+    view = torch.empty(len(b) + 16, dtype=torch.uint8, device="cuda")[4:4 + len(b)]
+    view.copy_(torch.frombuffer(bytearray(b), dtype=torch.uint8))
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
+@pytest.mark.parametrize("acc_on", ["host", "cuda"])
+def test_staged_columns_and_accumulator(acc_on):
+    """What the kernel cannot use in place is staged: one host object as a
+    fixed and as an advice column, a device column and a device accumulator
+    that are not 16-byte aligned."""
+    q, n = Q(), 8
+    S = table_system(n, seed=7)
+    ci = S["circuits"][0]
+    ci["fixed"][1] = ci["advice"][1]
+    g = fresh_graph()
+    both = g.add_calculation(q.SUB, (q.FIXED, 1, 0), (q.ADVICE, 1, g.add_rotation(1)))
+    g.add_calculation(q.HORNER, (q.PREVIOUS_VALUE, 0, 0), (q.Y, 0, 0), [(q.INTERMEDIATE, 0, 0), both, (q.ADVICE, 2, 0)])
+    shared = R.encode(F, ci["advice"][1])
+    acc = R.rand(13, n, F)
+    arg = R.encode(F, acc) if acc_on == "host" else cuda_off_by_4(R.encode(F, acc))
+    got = q.quotient_evaluate_part(
+        F.name, n, q.GATES, arg, theta=fr(S["theta"]), beta=fr(S["beta"]), gamma=fr(S["gamma"]), y=fr(S["y"]),
+        fixed=[R.encode(F, ci["fixed"][0]), shared],
+        advice=[R.encode(F, ci["advice"][0]), shared, cuda_off_by_4(R.encode(F, ci["advice"][2]))],
+        instance=[R.encode(F, x) for x in ci["instance"]], challenges=[fr(x) for x in ci["challenges"]], graph=g)
+    if acc_on == "cuda":
+        assert got is arg
+        got = bytes(got.cpu().numpy())
+    assert got == want_gates(S, g, acc)
+
+
 # --- the closed forms ---------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def golden():
