@@ -54,6 +54,7 @@ class ByteReader {
     return r;
   }
   size_t offset() const { return off_; }
+  size_t remaining() const { return n_ - off_; }
   void seek(size_t off) {
     if (off > n_) throw std::runtime_error("circom: seek past end of file");
     off_ = off;
@@ -110,6 +111,9 @@ struct ZKey {
   size_t num_witness() const { return (size_t)num_vars - num_public - 1; }
 };
 
+// The readers are defined in circom_parse.h (what they refuse is listed
+// there) and instantiated for both curves in groth16.hip.
+//
 // Peek the curve of a zkey (from the Groth header's base-field modulus).
 CurveId zkey_curve(const uint8_t* data, size_t len);
 

@@ -7,146 +7,12 @@
 #include <exception>
 #include <thread>
 
+#include "circom_parse.h"
+
 namespace tachyon_amd {
 namespace circom {
 
-namespace {
-
-void check_magic(ByteReader& rd, const char* magic, uint32_t want_version, const char* what) {
-  const uint8_t* m = rd.ptr(4);
-  if (memcmp(m, magic, 4) != 0) throw std::runtime_error(std::string("circom: not a ") + what + " file (bad magic)");
-  uint32_t version = rd.read<uint32_t>();
-  if (version != want_version)
-    throw std::runtime_error(std::string("circom: unsupported ") + what + " version " + std::to_string(version));
-}
-
-const std::pair<size_t, size_t>& section(const std::map<uint32_t, std::pair<size_t, size_t>>& secs, uint32_t id) {
-  auto it = secs.find(id);
-  if (it == secs.end()) throw std::runtime_error("circom: missing section " + std::to_string(id));
-  return it->second;
-}
-
-template <class T>
-void read_array(ByteReader& rd, std::vector<T>* out, size_t count) {
-  out->resize(count);
-  if (count) rd.take(out->data(), count * sizeof(T));
-}
-
-template <class F>
-struct BaseCfgOf {
-  using type = typename F::Config;
-};
-template <class B>
-struct BaseCfgOf<Fp2<B>> {
-  using type = typename B::Config;
-};
-
-}  // namespace
-
-CurveId zkey_curve(const uint8_t* data, size_t len) {
-  ByteReader rd(data, len);
-  check_magic(rd, "zkey", 1, "zkey");
-  auto secs = read_sections(rd);
-  auto [off, size] = section(secs, 2);
-  ByteReader g(data + off, size);
-  uint32_t n8q = g.read<uint32_t>();
-  const uint8_t* q = g.ptr(n8q);
-  if (modulus_matches<consts::bn254_fq>(q, n8q)) return CurveId::kBn254;
-  if (modulus_matches<consts::bls12_381_fq>(q, n8q)) return CurveId::kBls12_381;
-  throw std::runtime_error("circom: zkey base field is neither BN254 nor BLS12-381");
-}
-
-template <class G1, class G2>
-ZKey<G1, G2> parse_zkey(const uint8_t* data, size_t len) {
-  using Z = ZKey<G1, G2>;
-  using Fr = typename Z::Fr;
-  Z z;
-  ByteReader rd(data, len);
-  check_magic(rd, "zkey", 1, "zkey");
-  auto secs = read_sections(rd);
-  {
-    auto [off, size] = section(secs, 1);  // header: prover type 1 = Groth16
-    ByteReader h(data + off, size);
-    if (h.read<uint32_t>() != 1) throw std::runtime_error("circom: zkey prover type is not Groth16");
-  }
-  {
-    auto [off, size] = section(secs, 2);
-    ByteReader g(data + off, size);
-    uint32_t n8q = g.read<uint32_t>();
-    if (!modulus_matches<typename BaseCfgOf<typename G1::F>::type>(g.ptr(n8q), n8q))
-      throw std::runtime_error("circom: zkey base field does not match the curve");
-    uint32_t n8r = g.read<uint32_t>();
-    if (!modulus_matches<typename Fr::Config>(g.ptr(n8r), n8r))
-      throw std::runtime_error("circom: zkey scalar field does not match the curve");
-    z.num_vars = g.read<uint32_t>();
-    z.num_public = g.read<uint32_t>();
-    z.domain_size = g.read<uint32_t>();
-    if (z.num_vars < z.num_public + 1) throw std::runtime_error("circom: zkey has fewer variables than inputs");
-    if (z.domain_size == 0 || (z.domain_size & (z.domain_size - 1)))
-      throw std::runtime_error("circom: zkey domain size is not a power of two");
-    z.alpha_g1 = g.read<typename Z::A1>();
-    z.beta_g1 = g.read<typename Z::A1>();
-    z.beta_g2 = g.read<typename Z::A2>();
-    z.gamma_g2 = g.read<typename Z::A2>();
-    z.delta_g1 = g.read<typename Z::A1>();
-    z.delta_g2 = g.read<typename Z::A2>();
-  }
-  auto points = [&](uint32_t id, auto* out, size_t count) {
-    auto [off, size] = section(secs, id);
-    ByteReader p(data + off, size);
-    read_array(p, out, count);
-  };
-  points(3, &z.ic, z.num_public + 1);
-  {
-    auto [off, size] = section(secs, 4);
-    ByteReader c(data + off, size);
-    uint32_t count = c.read<uint32_t>();
-    z.coefficients.resize(count);
-    for (uint32_t i = 0; i < count; ++i) {
-      auto& e = z.coefficients[i];
-      e.matrix = c.read<uint32_t>();
-      e.constraint = c.read<uint32_t>();
-      e.signal = c.read<uint32_t>();
-      Fr raw;
-      c.take(&raw, sizeof(Fr));
-      // zkey.h:219-220: value = F::FromMontgomery(value.ToBigInt()), i.e. the
-      // stored word times R^-1 becomes the Montgomery representation
-      e.value = raw.from_mont();
-    }
-  }
-  points(5, &z.a1, z.num_vars);
-  points(6, &z.b1, z.num_vars);
-  points(7, &z.b2, z.num_vars);
-  points(8, &z.c1, z.num_witness());
-  points(9, &z.h1, z.domain_size);
-  return z;
-}
-
-template <class Fr>
-std::vector<Fr> parse_wtns(const uint8_t* data, size_t len) {
-  ByteReader rd(data, len);
-  check_magic(rd, "wtns", 2, "wtns");
-  auto secs = read_sections(rd);
-  uint32_t count;
-  {
-    auto [off, size] = section(secs, 1);
-    ByteReader h(data + off, size);
-    uint32_t n8 = h.read<uint32_t>();
-    if (!modulus_matches<typename Fr::Config>(h.ptr(n8), n8))
-      throw std::runtime_error("circom: wtns field does not match the curve's scalar field");
-    count = h.read<uint32_t>();
-  }
-  auto [off, size] = section(secs, 2);
-  ByteReader d(data + off, size);
-  std::vector<Fr> out(count);
-  for (uint32_t i = 0; i < count; ++i) {
-    Fr raw;
-    d.take(&raw, sizeof(Fr));
-    out[i] = raw.to_mont();  // wtns.h:116: F(witnesses[i].value()) -- canonical in, Montgomery out
-  }
-  return out;
-}
-
+// the readers (circom_parse.h), instantiated here for both curves
 template ZKey<Bn254G1, Bn254G2> parse_zkey<Bn254G1, Bn254G2>(const uint8_t*, size_t);
 template ZKey<Bls381G1, Bls381G2> parse_zkey<Bls381G1, Bls381G2>(const uint8_t*, size_t);
 template std::vector<Bn254Fr> parse_wtns<Bn254Fr>(const uint8_t*, size_t);

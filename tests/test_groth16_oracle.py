@@ -12,6 +12,10 @@
     circomlib/circuit/adder_data.json {a: 3, b: 4} derived from the key's
     own constraints (adder_witness): its proofs verify, a wrong public output
     does not, and the 32-bit wrap-around case verifies too;
+  * a trapdoor key larger than the fixtures with a dense R1CS
+    (groth16_synth.trapdoor_zkey: 16 signals, a full 16-row domain, 12 terms a
+    side, identity query points): the oracle's proofs verify for every
+    zero / non-zero combination of the blinding factors, a wrong witness fails;
   * the numpy/C path used at BASELINE configs[4]'s size (prove_np) equals the
     step-by-step restatement on synthetic keys.
 """
@@ -139,3 +143,37 @@ def test_prove_np_equals_restatement(curve, log_n, seed):
     assert OG.witness_map_np(zb, fb).tobytes() == b"".join(Fr.to_bytes(x) for x in h)
     assert OG.prove_np(zb, fb) == OG.prove(zk, full, h=h)
     assert OG.prove_np(zb, fb, 11, 13) == OG.prove(zk, full, 11, 13, h=h)
+
+
+@pytest.fixture(scope="module")
+def trapdoor():
+    import sys
+    sys.path.insert(0, os.path.dirname(__file__))
+    from groth16_synth import trapdoor_fixture
+    zb, w = trapdoor_fixture()
+    return CF.parse_zkey(zb), w
+
+
+def test_trapdoor_key_shape(trapdoor):
+    """A full domain of 16, and the identity query points the circuit's unused signals give."""
+    zk, w = trapdoor
+    assert (zk["num_vars"], zk["num_public"], zk["domain_size"]) == (16, 4, 16)
+    zero = lambda name: [i for i, b in enumerate(zk[name]) if not any(b)]
+    assert zero("a1") == [5, 15] and zero("b1") == [6, 15] and zero("b2") == [6, 15]
+    assert zero("c1") == [15 - 5] and zero("ic") == [] and zero("h1") == []
+    assert len(zk["coefficients"]) == 11 * 24 + 5
+    assert all(0 < x < P.BN254_FR for x in w[1:])
+
+
+@pytest.mark.parametrize("r_blind,s_blind", [(0, 0), (0x5EED, 0), (0, P.BN254_FR - 3), (0xC0FFEE, P.BN254_FR - 9)])
+def test_trapdoor_key_proofs_verify(trapdoor, r_blind, s_blind):
+    zk, w = trapdoor
+    assert verify(zk, w[1:5], OG.prove(zk, w, r_blind, s_blind))
+
+
+def test_trapdoor_key_wrong_witness_fails(trapdoor):
+    zk, w = trapdoor
+    bad = list(w)
+    bad[7] = (bad[7] + 1) % P.BN254_FR  # one witness signal: its rows no longer hold
+    assert not verify(zk, bad[1:5], OG.prove(zk, bad))
+    assert not verify(zk, [w[1] + 1] + w[2:5], OG.prove(zk, w))  # and a proof does not carry over to other inputs
