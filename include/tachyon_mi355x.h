@@ -924,6 +924,12 @@ TACHYON_C_EXPORT void tachyon_mi355x_msm_gpu_set_window_bits(int curve, void* ct
  * window bits forced, and with one or two windows per sort group set
  * (_set_variant bits 2-3 = 1 or 2; 3, all windows in one group, is accepted). */
 TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_set_mixed_windows(int curve, void* ctx, unsigned windows);
+/* The running-sum segment length of BN254 G1's window sums for the later runs
+ * of the context (tests and tuning): a power of two from 2 to 256, cut to the
+ * buckets of a window; 0 = the size's own.  Other curves keep the setting and
+ * do not read it.  Every length computes the same MSM.  Returns 1, or 0
+ * (nothing changed) for another length. */
+TACHYON_C_EXPORT int tachyon_mi355x_msm_gpu_set_window_segment(int curve, void* ctx, unsigned length);
 /* The layout of `windows` mixed-width windows for the curve's scalar field (no
  * GPU needed): c_lo, the number of wide windows (the top ones), the sort-key
  * bits, and windows + 1 bit offsets and bucket offsets (the last = the totals).

@@ -150,6 +150,7 @@ SIGNATURES = [
     ("tachyon_mi355x_msm_gpu_batch_affine", i32, [i32, vp, vp, sz, vp, sz, vp]),
     ("tachyon_mi355x_msm_gpu_plan_windows", ctypes.c_uint, [i32, vp, sz]),
     ("tachyon_mi355x_msm_gpu_set_mixed_windows", i32, [i32, vp, ctypes.c_uint]),
+    ("tachyon_mi355x_msm_gpu_set_window_segment", i32, [i32, vp, ctypes.c_uint]),
     ("tachyon_mi355x_msm_mixed_layout", i32, [i32, ctypes.c_uint] + [vp] * 5),
     ("tachyon_mi355x_msm_gpu_fold_bases", i32, [i32, vp, vp, sz, ctypes.c_uint, vp]),
     ("tachyon_mi355x_msm_gpu_folded_affine", i32, [i32, vp, vp, vp, sz, ctypes.c_uint, vp]),

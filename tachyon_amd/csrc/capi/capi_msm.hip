@@ -593,6 +593,14 @@ int tachyon_mi355x_msm_gpu_set_mixed_windows(int curve, void* ctx, unsigned wind
   GUARD_END
   return 1;
 }
+int tachyon_mi355x_msm_gpu_set_window_segment(int curve, void* ctx, unsigned length) {
+  if (!ctx || curve < 0 || curve > 3) return 0;
+  if (length && (length < 2 || length > 256 || (length & (length - 1)))) return 0;  // refused, nothing changed
+  GUARD_BEGIN
+  CURVE_DISPATCH(curve, static_cast<MsmCtx<C>*>(ctx)->set([&](auto& m) { m.set_window_segment(length); }))
+  GUARD_END
+  return 1;
+}
 int tachyon_mi355x_msm_mixed_layout(int curve, unsigned windows, unsigned* c_lo, unsigned* n_wide, unsigned* key_bits,
                                     unsigned* bit_offsets, unsigned* bucket_offsets) {
   if (curve < 0 || curve > 3) return 0;

@@ -212,7 +212,8 @@ inline void MsmPlan::size_for(size_t n) {
     ++p.levels;
   }
   // the window sums' segment lengths (mixed widths: window_sums takes them per
-  // width class, by the same rule)
+  // width class, by the same rule; BN254 G1's 29-bit sums lengthen a capped
+  // one until the segment threads fit the device, MsmGpu::pass29)
   p.seg = seg_for(p.active(), p.buckets);
   p.seg_tree = seg_tree_for(p.active(), p.buckets);
 }
@@ -351,6 +352,15 @@ class MsmGpu {
     mixed_w_ = W;
   }
   unsigned mixed_windows() const { return mixed_w_; }
+  // The segment length of BN254 G1's 29-bit window sums for later runs (0 =
+  // the rule's, pass29): a power of two from 2 to kSeg29Max, cut to the
+  // buckets of a narrow window.  Every length computes the same MSM.
+  void set_window_segment(unsigned L) {
+    if (L && (L < 2 || L > kSeg29Max || (L & (L - 1))))
+      throw std::runtime_error("tachyon_mi355x: a window segment length is a power of two from 2 to 256");
+    seg_force_ = L;
+  }
+  unsigned window_segment() const { return seg_force_; }
   // kernel-variant bits for in-process A/B tuning (0 = default)
   // A/B tuning knobs (bits 0-5, 7-20, 22 -- the FIPS reductions instead of
   // the limb-field ones; see run_windows --, 23 two-level and 24 two-pass
@@ -407,6 +417,7 @@ class MsmGpu {
   void join(const Shape& s, const Buffers& b, const ReduceKernels& rk);
   void window_sums_two_level(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows);
   void window_sums_by_trees(const Shape& s, const Buffers& b, Point* d_windows);
+  void window_sums29(const Shape& s, const Buffers& b, Point* d_windows);
   void window_sums(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows);
   void window_sums_by_segments(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows);
   Point run_host_pipelined(const void* bases, const void* scalars, size_t n, size_t chunks);
@@ -438,6 +449,19 @@ class MsmGpu {
   // hold for the two classes of a layout (`narrow` windows of B buckets, W -
   // narrow of 2 B) -- the larger class's, a class that goes by the scan having
   // none.  The one count window_sums allocates by and work_bytes estimates by.
+  // (BN254 G1's 29-bit window sums take both classes in one pass instead:
+  // pass29, by which window_sums29 launches and allocates and work_bytes
+  // estimates -- the windows that go by the scan, then `W` windows from
+  // `first` on by segments of L buckets, `narrow` of them with B buckets and
+  // the others with 2 B, `sums` segment sums in all)
+  struct Pass29 {
+    unsigned scan_lo, scan_hi, first, narrow, W, L;
+    size_t sums;
+  };
+  static constexpr unsigned kSeg29Max = 256;
+  static bool sums_by_pass29(const AccFields& f);
+  static size_t resident_threads29(bool raw);
+  Pass29 pass29(unsigned narrow, unsigned W, unsigned B, unsigned seg, bool raw) const;
   static unsigned class_seg(unsigned windows, unsigned buckets);
   static size_t mixed_seg_sums(const AccFields& f, unsigned narrow, unsigned W, unsigned B);
   // The sort of a run's entries (enqueue) and what its scratch takes
@@ -469,6 +493,7 @@ class MsmGpu {
   bool profile_ = false;
   unsigned force_c_ = 0;
   unsigned mixed_w_ = 0;  // set_mixed_windows
+  unsigned seg_force_ = 0;  // set_window_segment
   int variant_ = 0;
   MsmTimings timings_;
   DeviceBuffer bases_, scalars_, ents_, ents2_, sort_tmp_, scan_tmp_, check_;

@@ -567,11 +567,9 @@ typename MsmGpu<Curve>::ReduceKernels MsmGpu<Curve>::reduce_kernels(bool raw) co
   }
   k.level[0][0] = k.level[0][1] = k.level[1][0] = k.level[1][1] = seg_reduce;
   if constexpr (std::is_same_v<Curve, Bn254G1>) {
-    if (f.acc29) {  // the 29-bit reductions with the 29-bit accumulation (bit 18 restores the FIPS field for both)
-      k.level[0][0] = k.level[0][1] = k.level[1][0] = k.level[1][1] = &seg_reduce29_kernel<false, false>;
-      k.win_segment = raw ? &window_segment29_kernel<true> : &window_segment29_kernel<false>;
-      k.win_reduce = &reduce_uniform29_kernel;
-    }
+    // the 29-bit reductions with the 29-bit accumulation (bit 18 restores the FIPS field for both; the window
+    // sums' 29-bit kernels take both window widths and are launched by window_sums29)
+    if (f.acc29) k.level[0][0] = k.level[0][1] = k.level[1][0] = k.level[1][1] = &seg_reduce29_kernel<false, false>;
     if (raw) {  // Raw pieces into level 0, Raw bucket sums out of the last level
       k.level[1][1] = &seg_reduce29_kernel<true, true>;
       k.level[1][0] = &seg_reduce29_kernel<true, false>;
@@ -808,15 +806,6 @@ void MsmGpu<Curve>::window_sums_by_segments(const Shape& s, const Buffers& b, co
   // (fan-in 16 -> 2 saved ~0.4 ms at 2^21..2^23)
   constexpr unsigned KW = 2;
   while (S > 1) {
-    // BN254 G1 (29-bit reductions): the binary levels until <= kBlock segment
-    // sums per window are left, then one launch for the rest of the tree
-    if constexpr (std::is_same_v<Curve, Bn254G1>) {
-      if (acc_.acc29 && S <= kBlock) {
-        hipLaunchKernelGGL(window_tree29_kernel, dim3(W), dim3(kBlock), 0, stream_, s_cur, S, d_windows);
-        TA_HIP(hipGetLastError());
-        break;
-      }
-    }
     unsigned S_out = (S + KW - 1) / KW;
     Point* dst = (S_out == 1) ? d_windows : s_nxt;
     hipLaunchKernelGGL(rk.win_reduce, dim3(grid_for(lanes * (size_t)W * S_out)), dim3(kBlock), 0, stream_, s_cur, W, S,
@@ -830,11 +819,71 @@ void MsmGpu<Curve>::window_sums_by_segments(const Shape& s, const Buffers& b, co
   }
 }
 
-// Mixed widths: one pass per width class over the class's contiguous buckets
-// -- B is uniform inside a class, so the kernels are the uniform ones, each
-// class with the segment lengths of its own window and bucket counts.
+// BN254 G1 over the 29-bit field: the window sums of both width classes in the
+// same launches (pass29 says which windows go by the scan and which by
+// segments of one length L): one segment pass, the binary levels until the
+// widest window has <= kBlock sums left, one tree launch for the rest.
+template <class Curve>
+void MsmGpu<Curve>::window_sums29(const Shape& s, const Buffers& b, Point* d_windows) {
+  if constexpr (std::is_same_v<Curve, Bn254G1>) {
+    const bool raw = s.sb.raw;
+    const Pass29 p = pass29(s.mixed ? s.narrow : s.W, s.W, s.B, s.seg, raw);
+    auto buckets_of = [&](unsigned w) {  // window w's first bucket: w, and the wide windows below it once more, times B
+      const unsigned units = w + (s.mixed && w > s.narrow ? w - s.narrow : 0u);
+      return reinterpret_cast<Point*>(reinterpret_cast<char*>(b.bucket_sum) + (size_t)units * s.B * s.sb.slot);
+    };
+    auto* scan = raw ? &window_scan29_kernel<true> : &window_scan29_kernel<false>;
+    if (p.scan_lo) {
+      hipLaunchKernelGGL(scan, dim3(p.scan_lo), dim3(kBlock), 0, stream_, b.bucket_sum, s.B, d_windows);
+      TA_HIP(hipGetLastError());
+    }
+    if (p.scan_hi) {
+      hipLaunchKernelGGL(scan, dim3(p.scan_hi), dim3(kBlock), 0, stream_, buckets_of(p.scan_lo), 2 * s.B,
+                         d_windows + p.scan_lo);
+      TA_HIP(hipGetLastError());
+    }
+    if (p.W == 0) return;
+    // the segment pass: windows [first, first + W), `narrow` of them with B buckets, the others with 2 B
+    Point* out = d_windows + p.first;
+    unsigned S = s.B / p.L;
+    const unsigned wide = p.W - p.narrow;
+    Point* s_cur = static_cast<Point*>(seg_a_.ensure(p.sums * sizeof(Point)));
+    Point* s_nxt = static_cast<Point*>(seg_b_.ensure(p.sums * sizeof(Point)));
+    auto* segment = raw ? &window_segment29_kernel<true> : &window_segment29_kernel<false>;
+    hipLaunchKernelGGL(segment, dim3(grid_for(p.sums)), dim3(kBlock), 0, stream_, buckets_of(p.first), p.W, p.narrow, s.B,
+                       p.L, s_cur);
+    TA_HIP(hipGetLastError());
+    // (these levels run a few hundred waves, latency-bound: fan-in 2, see window_sums_by_segments)
+    while ((wide ? 2 * S : S) > kBlock) {
+      if (wide && (S & 1)) throw std::runtime_error("tachyon_mi355x: odd segment count under windows of two widths");
+      hipLaunchKernelGGL(reduce_uniform29_kernel, dim3(grid_for((size_t)p.narrow * ((S + 1) / 2) + (size_t)wide * S)),
+                         dim3(kBlock), 0, stream_, s_cur, p.W, p.narrow, S, 2u, s_nxt);
+      TA_HIP(hipGetLastError());
+      std::swap(s_cur, s_nxt);
+      S = (S + 1) / 2;
+    }
+    hipLaunchKernelGGL(window_tree29_kernel, dim3(p.W), dim3(kBlock), 0, stream_, s_cur, p.narrow, S, out);
+    TA_HIP(hipGetLastError());
+  }
+}
+
+// Mixed widths (all but BN254 G1's 29-bit field, window_sums29): one pass per
+// width class over the class's contiguous buckets -- B is uniform inside a
+// class, so the kernels are the uniform ones, each class with the segment
+// lengths of its own window and bucket counts.
 template <class Curve>
 void MsmGpu<Curve>::window_sums(const Shape& s, const Buffers& b, const ReduceKernels& rk, Point* d_windows) {
+  if (sums_by_pass29(acc_)) {
+    if (!s.mixed && (variant_ & (1u << 19)) && !window_sums_by_scan(acc_, s.B) && s.B / s.seg <= kBlock) {
+      if constexpr (std::is_same_v<Curve, Bn254G1>) {
+        auto* segtree = s.sb.raw ? &window_segtree29_kernel<true> : &window_segtree29_kernel<false>;
+        hipLaunchKernelGGL(segtree, dim3(s.W), dim3(kBlock), 0, stream_, b.bucket_sum, s.B, s.seg, d_windows);
+        TA_HIP(hipGetLastError());
+      }
+      return;
+    }
+    return window_sums29(s, b, d_windows);
+  }
   if (s.mixed) {
     const unsigned classes[2][3] = {{0, s.narrow, s.B}, {s.narrow, s.W - s.narrow, 2 * s.B}};  // first window, windows, B
     // the segment sums of both classes share seg_a_ / seg_b_: sized for the larger
@@ -859,21 +908,6 @@ void MsmGpu<Curve>::window_sums(const Shape& s, const Buffers& b, const ReduceKe
   }
   if (rk.seg1 && (variant_ & (1 << 23)) && !acc_.tree_reduce) return window_sums_two_level(s, b, rk, d_windows);
   if (acc_.tree_reduce) return window_sums_by_trees(s, b, d_windows);
-  if constexpr (std::is_same_v<Curve, Bn254G1>) {
-    const bool raw = s.sb.raw;
-    if (window_sums_by_scan(acc_, s.B)) {
-      auto* scan = raw ? &window_scan29_kernel<true> : &window_scan29_kernel<false>;
-      hipLaunchKernelGGL(scan, dim3(s.W), dim3(kBlock), 0, stream_, b.bucket_sum, s.B, d_windows);
-      TA_HIP(hipGetLastError());
-      return;
-    }
-    if (acc_.acc29 && (variant_ & (1u << 19)) && s.B / s.seg <= kBlock) {
-      auto* segtree = raw ? &window_segtree29_kernel<true> : &window_segtree29_kernel<false>;
-      hipLaunchKernelGGL(segtree, dim3(s.W), dim3(kBlock), 0, stream_, b.bucket_sum, s.B, s.seg, d_windows);
-      TA_HIP(hipGetLastError());
-      return;
-    }
-  }
   window_sums_by_segments(s, b, rk, d_windows);
 }
 
@@ -1105,6 +1139,60 @@ unsigned MsmGpu<Curve>::class_seg(unsigned windows, unsigned buckets) {
 }
 
 template <class Curve>
+bool MsmGpu<Curve>::sums_by_pass29(const AccFields& f) {
+  return std::is_same_v<Curve, Bn254G1> && f.acc29 && !f.tree_reduce;
+}
+
+// Threads of window_segment29_kernel the device holds at once: the kernel's
+// resident blocks per CU (as the runtime prices its registers) times the CUs.
+template <class Curve>
+size_t MsmGpu<Curve>::resident_threads29(bool raw) {
+  static size_t cached[2] = {0, 0};  // (every device of a process is the same part)
+  if constexpr (std::is_same_v<Curve, Bn254G1>) {
+    if (!cached[raw]) {
+      int dev = 0, cus = 0, blocks = 0;
+      TA_HIP(hipGetDevice(&dev));
+      TA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+      auto* segment = raw ? &window_segment29_kernel<true> : &window_segment29_kernel<false>;
+      TA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, segment, (int)kBlock, 0));
+      cached[raw] = (size_t)std::max(1, blocks) * std::max(1, cus) * kBlock;
+    }
+  }
+  return cached[raw];
+}
+
+// How window_sums29 covers `narrow` windows of B buckets and W - narrow of 2 B:
+// a class with at most kBlock buckets per window goes by the scan, the other
+// windows by segments of one length L.  L is `seg`, the small-MSM rule's
+// (MsmPlan::seg_for); where that rule stops at its cap of 64 although the
+// segment threads still need more than one resident round of the kernel, L
+// doubles until they fit one (the rounds of the serial chain set the time, not
+// the additions: 2^26, 15.7 M buckets: L = 128, 122,880 threads), up to
+// kSeg29Max.  set_window_segment overrides it (tests, tuning).
+template <class Curve>
+typename MsmGpu<Curve>::Pass29 MsmGpu<Curve>::pass29(unsigned narrow, unsigned W, unsigned B, unsigned seg,
+                                                     bool raw) const {
+  Pass29 p{};
+  p.narrow = narrow, p.W = W;
+  if (B <= kBlock) {  // the narrow class by the scan (window_sums_by_scan)
+    p.scan_lo = narrow, p.first = narrow, p.narrow = 0, p.W = W - narrow;
+    if (2 * B <= kBlock) p.scan_hi = p.W, p.first = W, p.W = 0;
+  }
+  if (p.W == 0) return p;
+  const size_t nb = ((size_t)p.narrow + 2 * (size_t)(p.W - p.narrow)) * B;
+  if (p.narrow != W) seg = MsmPlan::seg_for(1, (unsigned)std::min<size_t>(nb, 1u << 31));  // both classes' buckets
+  if (seg_force_) {
+    seg = seg_force_;
+  } else if (seg == 64) {
+    const size_t resident = resident_threads29(raw);
+    while (seg < kSeg29Max && nb / seg > resident) seg *= 2;
+  }
+  p.L = std::min(seg, B);
+  p.sums = nb / p.L;
+  return p;
+}
+
+template <class Curve>
 size_t MsmGpu<Curve>::mixed_seg_sums(const AccFields& f, unsigned narrow, unsigned W, unsigned B) {
   const unsigned classes[2][2] = {{narrow, B}, {W - narrow, 2 * B}};  // windows, buckets per window
   size_t sums = 0;
@@ -1268,7 +1356,10 @@ size_t MsmGpu<Curve>::work_bytes(size_t n, unsigned c, size_t batch) const {
   bytes += batch * p.total_buckets() * slot;                                // bucket sums
   // segment sums (x2), where the window sums are not one scan launch per window
   // (mixed widths: the two width classes share them, mixed_seg_sums)
-  if (p.mixed)
+  // (BN254 G1's 29-bit window sums: the one pass over both classes, pass29)
+  if (sums_by_pass29(acc_fields(variant_)))
+    bytes += 2 * pass29(p.mixed ? p.narrow() : W, W, p.buckets, p.seg, sb.raw).sums * sizeof(Point);
+  else if (p.mixed)
     bytes += 2 * mixed_seg_sums(acc_fields(variant_), p.narrow(), p.windows, p.buckets) * sizeof(Point);
   else if (!window_sums_by_scan(acc_fields(variant_), p.buckets))
     bytes += 2 * batch * p.active() * (p.buckets / p.seg) * sizeof(Point);

@@ -85,6 +85,9 @@ class MsmMultiDevice {
   void set_mixed_windows(unsigned W) {
     for (auto& s : shards_) s->msm->set_mixed_windows(W);
   }
+  void set_window_segment(unsigned L) {
+    for (auto& s : shards_) s->msm->set_window_segment(L);
+  }
   void set_variant(int v) {
     for (auto& s : shards_) s->msm->set_variant(v);
   }
@@ -94,6 +97,7 @@ class MsmMultiDevice {
   void copy_settings(const MsmGpu<Curve>& from) {
     set_force_window_bits(from.force_window_bits());
     set_mixed_windows(from.mixed_windows());
+    set_window_segment(from.window_segment());
     set_variant(from.variant());
     set_profile(from.profile());
   }

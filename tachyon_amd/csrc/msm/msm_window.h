@@ -271,19 +271,32 @@ __global__ __launch_bounds__(kBlock, 2) void reduce_uniform_pair_kernel(const XY
   Ar::store(reinterpret_cast<Fb*>(out), t, h, acc);
 }
 
-// BN254 G1 over the 29-bit field (see seg_reduce29_kernel, msm_join.h)
+// BN254 G1 over the 29-bit field (see seg_reduce29_kernel, msm_join.h).
+// One pass over the windows of both widths: windows [0, narrow) have B
+// buckets, windows [narrow, W) 2 B (MsmPlan::make_mixed; the uniform plan is
+// narrow = W).  L divides B, so the segments tile the concatenated bucket
+// array: thread t owns buckets [t L, (t + 1) L), segment j of its window by
+// the closed forms of recode_scalar / bucket_of_key, and the segment sums come
+// out window-major (S = B / L per narrow window, 2 S per wide one).  The load
+// of bucket k - 1 is issued before the two additions of bucket k: at two waves
+// per SIMD nothing else hides the 144-byte gather.
 template <bool kRaw>
 __global__ __launch_bounds__(kBlock, 2) void window_segment29_kernel(const XYZZ<Bn254Fq>* __restrict__ bucket_sum,
-                                                                    unsigned W, unsigned B, unsigned L,
+                                                                    unsigned W, unsigned narrow, unsigned B, unsigned L,
                                                                     XYZZ<Bn254Fq>* __restrict__ out) {
   const uint32_t S = B / L;
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= W * S) return;
-  const uint32_t w = t / S, j = t - w * S;
-  const size_t b0 = (size_t)w * B + (size_t)j * L;
+  const uint32_t lo = narrow * S;  // segments of the narrow windows
+  if (t >= lo + (W - narrow) * 2 * S) return;
+  const uint32_t j = t < lo ? t % S : (t - lo) % (2 * S);
+  const size_t b0 = (size_t)t * L;
+  auto load = [&](size_t i) { return kRaw ? acc29::load_raw(bucket_sum, i) : acc29::load_pt(bucket_sum, i); };
   acc29::Pt R{acc29::Acc{}, true}, acc = R;
+  acc29::Pt next = load(b0 + L - 1);
   for (int k = (int)L - 1; k >= 0; --k) {
-    R = acc29::add(R, kRaw ? acc29::load_raw(bucket_sum, b0 + k) : acc29::load_pt(bucket_sum, b0 + k));
+    const acc29::Pt cur = next;
+    if (k > 0) next = load(b0 + k - 1);
+    R = acc29::add(R, cur);
     acc = acc29::add(acc, R);
   }
   acc = acc29::add(acc, acc29::small_mul(R, j * L));
@@ -296,14 +309,17 @@ __global__ __launch_bounds__(kBlock, 2) void window_segment29_kernel(const XYZZ<
 // mostly one latency-bound addition).  (Computing the segment sums in this
 // kernel too, window_segment29_kernel's loop, gave wrong window sums on the
 // GPU although the loop is the same code -- not understood, so not used.)
-__global__ __launch_bounds__(kBlock, 2) void window_tree29_kernel(const XYZZ<Bn254Fq>* __restrict__ in, unsigned S,
-                                                                 XYZZ<Bn254Fq>* __restrict__ out) {
+__global__ __launch_bounds__(kBlock, 2) void window_tree29_kernel(const XYZZ<Bn254Fq>* __restrict__ in, unsigned narrow,
+                                                                 unsigned S, XYZZ<Bn254Fq>* __restrict__ out) {
   __shared__ acc29::Raw sh[kBlock];
   const uint32_t w = blockIdx.x, j = threadIdx.x;
+  // window w's sums: S of them below `narrow`, 2 S from there on (window_segment29_kernel)
+  const uint32_t Sw = w < narrow ? S : 2 * S;
+  const size_t first = w < narrow ? (size_t)w * S : (size_t)narrow * S + (size_t)(w - narrow) * 2 * S;
   acc29::Pt v{acc29::Acc{}, true};
-  if (j < S) v = acc29::load_pt(in, (size_t)w * S + j);
+  if (j < Sw) v = acc29::load_pt(in, first + j);
   unsigned span = 1;
-  while (span < S) span <<= 1;
+  while (span < Sw) span <<= 1;
   for (unsigned half = span >> 1; half >= 1; half >>= 1) {
     if (j >= half && j < 2 * half) acc29::store_raw(sh, j - half, v);
     __syncthreads();
@@ -376,15 +392,26 @@ __global__ __launch_bounds__(kBlock, 2) void window_scan29_kernel(const XYZZ<Bn2
   if (j == 0) acc29::store_pt(out, w, v);
 }
 
+// (windows [0, narrow) hold S_in sums each, windows [narrow, W) 2 S_in, in and
+// out window-major as window_segment29_kernel writes them)
 __global__ __launch_bounds__(kBlock, 2) void reduce_uniform29_kernel(const XYZZ<Bn254Fq>* __restrict__ in, unsigned W,
-                                                                    unsigned S_in, unsigned K2,
+                                                                    unsigned narrow, unsigned S_in, unsigned K2,
                                                                     XYZZ<Bn254Fq>* __restrict__ out) {
-  const uint32_t S_out = (S_in + K2 - 1) / K2;
+  const uint32_t out_lo = (S_in + K2 - 1) / K2, out_hi = (2 * S_in + K2 - 1) / K2;
   const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= W * S_out) return;
-  const uint32_t w = t / S_out, q = t - w * S_out;
-  const uint32_t e0 = q * K2, e1 = min(S_in, e0 + K2);
-  const XYZZ<Bn254Fq>* src = in + (size_t)w * S_in;
+  const uint32_t lo = narrow * out_lo;
+  if (t >= lo + (W - narrow) * out_hi) return;
+  uint32_t q, S;
+  size_t first;
+  if (t < lo) {
+    const uint32_t w = t / out_lo;
+    q = t - w * out_lo, S = S_in, first = (size_t)w * S_in;
+  } else {
+    const uint32_t w = (t - lo) / out_hi;
+    q = (t - lo) - w * out_hi, S = 2 * S_in, first = (size_t)narrow * S_in + (size_t)w * 2 * S_in;
+  }
+  const uint32_t e0 = q * K2, e1 = min(S, e0 + K2);
+  const XYZZ<Bn254Fq>* src = in + first;
   acc29::Pt acc = acc29::load_pt(src, e0);
   for (uint32_t e = e0 + 1; e < e1; ++e) acc = acc29::add(acc, acc29::load_pt(src, e));
   acc29::store_pt(out, t, acc);

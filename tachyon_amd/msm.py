@@ -215,6 +215,14 @@ class VariableBaseMSMGpu:
             raise ValueError(f"{windows} mixed-width windows refused (widths of 2 to 26 bits, at most 24 key bits)")
         self.mixed_windows = windows
 
+    def set_window_segment(self, length: int):
+        """The running-sum segment length of BN254 G1's window sums for later
+        runs (tests and tuning): a power of two from 2 to 256, 0 = the size's
+        own (tachyon_mi355x_msm_gpu_set_window_segment).  The result does not
+        depend on it."""
+        if not lib().tachyon_mi355x_msm_gpu_set_window_segment(self.curve_id, self._ctx, length):
+            raise ValueError(f"window segment length {length} refused (a power of two from 2 to 256, or 0)")
+
     def set_profile(self, on: bool):
         lib().tachyon_mi355x_msm_gpu_set_profile(self.curve_id, self._ctx, 1 if on else 0)
 
