@@ -1329,6 +1329,75 @@ TACHYON_C_EXPORT size_t tachyon_mi355x_grand_product_tile_rows(void);
 TACHYON_C_EXPORT size_t tachyon_mi355x_grand_product_walk_tiles(void);
 TACHYON_C_EXPORT void tachyon_mi355x_grand_product_last_timings(float* out_ms);
 
+/* Log-derivative lookup: the multiplicities m(X) and the grand sum phi(X) of
+ * zk/lookup/log_derivative_halo2/prover_impl.h:99-155 (ComputeMPoly,
+ * ComputeMPolys) and :186-316 (ComputeLogDerivatives, CreateGrandSumPoly,
+ * CreateGrandSumPolys) on columns that stay in device memory.  beta is drawn
+ * after the m polynomials are committed, hence two calls.
+ *
+ * A lookup has num_inputs >= 1 compressed input columns f_0 .. f_{K-1} and
+ * one compressed table column t; u = usable_rows of n rows; `count` runs over
+ * all lookups of all circuits, which the caller flattens.
+ *
+ * m_polys: the entries (i, t[i] as a canonical integer) for i < u are sorted
+ * by the integer alone, ties by ascending i (base::StableSort).  For every
+ * input column and row j < u the canonical value of f_k[j] is searched with
+ * BinarySearchByKey (base/containers/container_util.h:169-185): left = 0,
+ * right = u, mid = left + (right - left) / 2, and the FIRST equal hit
+ * returns.  A hit adds 1 to the counter of that entry's original row; a miss
+ * adds nothing and is no error.  With duplicate table values the row that
+ * receives the count is the one this bisection lands on.  out_m[l][i] = the
+ * counter for i < u and 0 for u <= i < n (m is not blinded); out_misses[l]
+ * (or null) = the input values of lookup l found nowhere in t[0..u).
+ *
+ * grand_sums: L[i] = sum_k 1 / (f_k[i] + beta) - m[i] / (t[i] + beta) for
+ * i < u, where a zero denominator contributes 0 (the batch inverse skips
+ * zeros, math/base/groups.h:124-143).  out_phi[l][0] = 0, out_phi[l][i] =
+ * sum_{j<i} L[j] for i < u, out_phi[l][u] = 0, and the rows u+1 .. n-1 receive
+ * that lookup's blinds in order (zk/base/blinder.h:33-45).  out_totals (or
+ * null): per lookup the sum of L over all u rows, which is 0 for a lookup
+ * that balances and is not part of the polynomial.
+ *
+ * Elements are 32-byte Montgomery values, canonical on output.  Columns, m,
+ * blinds (per lookup n - usable_rows - 1 elements, lookup after lookup),
+ * out_m[l], out_phi[l] (n elements each) and out_totals are host or device
+ * memory; beta, the descriptor arrays and out_misses are host memory.  Inputs
+ * are never written.
+ *
+ * Both return 1, or 0 with nothing written and no GPU call made when: field
+ * is not 0 (bn254 Fr) or 2 (bls12-381 Fr); n is no power of two, n < 2 or
+ * n > 2^30; usable_rows == 0 or usable_rows >= n; a lookup has no inputs; an
+ * array or a column is null with a nonzero count (blinds only when
+ * n - usable_rows - 1 > 0), or beta is null; an output overlaps an input, a
+ * table, an m or another output.  The blinds are taken to hold exactly
+ * n - usable_rows - 1 elements per phi: capi/log_lookup_validate.h refuses
+ * any other count for a caller that knows the array's length, as the Python
+ * binding does.  A HIP failure, more than 2^32 - 1 (input, row) pairs in one
+ * lookup or more than 2^30 workgroups in one launch return 0 with a message
+ * on stderr; the calls never abort.
+ *
+ * tile_rows: the rows one workgroup of the grand sum owns (the carry scan
+ * takes 256 tile sums per step).  work_bytes: the device memory the larger of
+ * the two calls holds for `count` lookups of at most max_inputs inputs with
+ * every column staged from the host (0 on a failure; needs a device).
+ * last_timings: 5 values, milliseconds (stream events) of the last calls'
+ * phases: sort, count (m_polys), sums A, B, C (grand_sums). */
+typedef struct {
+  const void* const* inputs;
+  size_t num_inputs;
+  const void* table;
+} tachyon_mi355x_log_lookup;
+TACHYON_C_EXPORT int tachyon_mi355x_log_lookup_m_polys(int field, size_t n, size_t usable_rows,
+                                                       const tachyon_mi355x_log_lookup* lookups, size_t count,
+                                                       void* const* out_m, uint64_t* out_misses);
+TACHYON_C_EXPORT int tachyon_mi355x_log_lookup_grand_sums(int field, size_t n, size_t usable_rows, const void* beta,
+                                                          const tachyon_mi355x_log_lookup* lookups,
+                                                          const void* const* m, size_t count, const void* blinds,
+                                                          void* const* out_phi, void* out_totals);
+TACHYON_C_EXPORT size_t tachyon_mi355x_log_lookup_tile_rows(void);
+TACHYON_C_EXPORT size_t tachyon_mi355x_log_lookup_work_bytes(size_t n, size_t max_inputs, size_t count);
+TACHYON_C_EXPORT void tachyon_mi355x_log_lookup_last_timings(float* out_ms);
+
 /* PLONK quotient: the vanishing argument's h(X) (zk/plonk/vanishing/
  * circuit_polynomial_builder.h:199-245, the Scroll shape; vanishing_utils.h:
  * 65-112, 167-196; vanishing_prover_impl.h:106-112) on device-resident

@@ -234,6 +234,14 @@ SIGNATURES = [
     ("tachyon_mi355x_quotient_tile_rows", sz, []),
     ("tachyon_mi355x_quotient_fast_slots", sz, []),
     ("tachyon_mi355x_quotient_last_timings", None, [fp]),
+    # log-derivative lookup: multiplicities m(X) and grand sum phi(X)
+    ("tachyon_mi355x_log_lookup_m_polys", i32, [i32, sz, sz, vp, sz, ctypes.POINTER(ctypes.c_void_p),
+                                                ctypes.POINTER(ctypes.c_uint64)]),
+    ("tachyon_mi355x_log_lookup_grand_sums", i32, [i32, sz, sz, vp, vp, ctypes.POINTER(ctypes.c_void_p), sz, vp,
+                                                   ctypes.POINTER(ctypes.c_void_p), vp]),
+    ("tachyon_mi355x_log_lookup_tile_rows", sz, []),
+    ("tachyon_mi355x_log_lookup_work_bytes", sz, [sz, sz, sz]),
+    ("tachyon_mi355x_log_lookup_last_timings", None, [fp]),
     # field-generic NTT domains
     ("tachyon_mi355x_ntt_domain_create", vp, [i32, sz]),
     ("tachyon_mi355x_ntt_domain_destroy", None, [vp]),

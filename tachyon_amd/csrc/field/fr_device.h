@@ -1,5 +1,5 @@
 // Device helpers for the 8-limb scalar fields: 16-byte element access, wave
-// shuffles and the workgroup's product scan.
+// shuffles and the workgroup's product and sum scans.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -88,6 +88,31 @@ __device__ __forceinline__ Fr block_scan_mul(const Fr& x, Fr* lds, Fr* total) {
   }
   *total = acc;
   return before * e;
+}
+
+// The same scan with sums, in thread order: returns the sum of x over the
+// threads before this one, *total the sum over all of them.
+template <class Fr, unsigned kBlock>
+__device__ __forceinline__ Fr block_scan_add(const Fr& x, Fr* lds, Fr* total) {
+  constexpr unsigned kWaves = kBlock / 64;
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Fr s = x;
+  for (unsigned d = 1; d < 64; d <<= 1) {
+    const Fr m = s + shfl_fr(s, lane - d);
+    if (lane >= d) s = m;
+  }
+  Fr e = shfl_fr(s, lane - 1);
+  if (lane == 0) e = Fr::zero();
+  __syncthreads();
+  if (lane == 63) lds[wave] = s;
+  __syncthreads();
+  Fr before = Fr::zero(), acc = Fr::zero();
+  for (unsigned i = 0; i < kWaves; ++i) {
+    if (i == wave) before = acc;
+    acc = acc + lds[i];
+  }
+  *total = acc;
+  return before + e;
 }
 
 }  // namespace tachyon_amd

@@ -7,6 +7,7 @@
 
 #include "../common/omega_table.h"
 #include "../field/fr_device.h"
+#include "tile_invert.h"
 
 namespace tachyon_amd::plonk {
 
@@ -138,21 +139,8 @@ __global__ __launch_bounds__(kGpBlock) void gp_ratio_kernel(const DevJob<Fr>* __
   }
 }
 
-// Pass A, tiles.  One lane per tile: the tile's one inversion, 64 of them per
-// wave side by side (a Fermat inversion is a chain of ~380 dependent
-// products: in the row kernel it held a whole workgroup's registers idle
-// behind one lane).  dens[t] <- 1 / P_t, prods[t] <- the product of the tile's
-// ratios.
-template <class Fr>
-__global__ __launch_bounds__(64) void gp_invert_kernel(Fr* __restrict__ dens, Fr* __restrict__ prods, uint32_t count) {
-  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= count) return;
-  const Fr p = load_fr(dens + i);
-  if (p.is_one()) return;  // a tile past the usable rows: 1 / 1, prods as it is
-  const Fr inv = p.inverse();  // a product of nonzero values
-  store_fr(dens + i, inv);
-  store_fr(prods + i, load_fr(prods + i) * inv);
-}
+// Pass A, tiles: tile_invert_kernel (tile_invert.h), one lane per tile.
+// dens[t] <- 1 / P_t, prods[t] <- the product of the tile's ratios.
 
 // Pass B.  One workgroup per chain: an exclusive product scan of the chain's
 // tile products (its jobs' tiles are consecutive), kGpWalk at a time, the
@@ -338,7 +326,7 @@ void GrandProduct<Fr>::launch(const Call& c, PhaseClock& clock) {
     hipLaunchKernelGGL(gp_ratio_kernel<Fr>, dim3((unsigned)tiles), dim3(kGpBlock), 0, stream_, d_jobs,
                        reinterpret_cast<const DevFactor<Fr>*>(c.d_meta + c.off_fac),
                        reinterpret_cast<const Fr*>(c.d_meta + c.off_tab), (uint32_t)c.u, (uint32_t)c.tpj, prods, dens);
-    hipLaunchKernelGGL(gp_invert_kernel<Fr>, dim3(ceil_div(tiles, 64)), dim3(64), 0, stream_, dens, prods,
+    hipLaunchKernelGGL(tile_invert_kernel<Fr>, dim3(ceil_div(tiles, 64)), dim3(64), 0, stream_, dens, prods,
                        (uint32_t)tiles);
   }
   clock.end();
