@@ -1398,6 +1398,66 @@ TACHYON_C_EXPORT size_t tachyon_mi355x_log_lookup_tile_rows(void);
 TACHYON_C_EXPORT size_t tachyon_mi355x_log_lookup_work_bytes(size_t n, size_t max_inputs, size_t count);
 TACHYON_C_EXPORT void tachyon_mi355x_log_lookup_last_timings(float* out_ms);
 
+/* Halo2 lookup: the permuted columns A' and S' of zk/lookup/halo2/
+ * permute_expression_pair.h:29-142 (PermuteExpressionPair, called from
+ * lookup/halo2/prover_impl.h:74-95) on columns that stay in device memory: the
+ * step between the compressed pair and tachyon_mi355x_lookup_grand_product.
+ *
+ * A pair is one lookup's compressed input column A and compressed table
+ * column S, n elements each, u = usable_rows of them used; `count` runs over
+ * all lookups of all circuits, which the caller flattens.  "Value order" is
+ * the order of the canonical integers (ToBigInt()), not of the Montgomery
+ * limbs.
+ *
+ *   A'[0..u) is A[0..u) in ascending value order.  Row i < u is a first row
+ *   when i = 0 or A'[i] != A'[i-1], else a repeated row; R = the number of
+ *   repeated rows, r(i) the rank of repeated row i among them by ascending i.
+ *   leftover[0..R) is the multiset S[0..u) less one instance of each distinct
+ *   value of A', in ascending value order.  S'[i] = A'[i] on a first row and
+ *   leftover[R - 1 - r(i)] on a repeated row (the reference hands the
+ *   leftover out in ascending order, each to the last repeated row not yet
+ *   served).  Rows u .. n-1 of A' and then of S' are the caller's blinds:
+ *   per pair n - u values for A' followed by n - u for S' (Blind with
+ *   include_last_row, zk/base/blinder.h:33-45), pair after pair.
+ *
+ * Outputs are the bytes of the elements they came from (Montgomery form, not
+ * reduced again).  out_misses[l] (or null) = the distinct values of A[0..u)
+ * of pair l found nowhere in S[0..u); the reference aborts on one.  Here a
+ * pair with misses has unspecified rows < u in its two outputs (its blind
+ * rows are still written, nothing is read or written out of bounds) and every
+ * other pair of the call is exact.
+ *
+ * Columns, blinds, out_input[l] and out_table[l] (n elements each) are host
+ * or device memory; the descriptor and pointer arrays and out_misses are host
+ * memory.  Inputs are never written.
+ *
+ * permute_pairs returns 1 when it ran, with or without misses, and 0 with
+ * nothing written and no GPU call made when: field is not 0 (bn254 Fr) or 2
+ * (bls12-381 Fr); n is no power of two, n < 2 or n > 2^30; usable_rows == 0
+ * or usable_rows >= n; an array, a column, an output or blinds is null with a
+ * nonzero count; an output overlaps another output or any column of the call.
+ * count == 0 returns 1 and makes no GPU call.  The blinds are taken to hold
+ * exactly 2 (n - usable_rows) elements per pair: capi/
+ * lookup_permute_validate.h refuses any other count for a caller that knows
+ * the array's length, as the Python binding does.  A HIP failure or more than
+ * 2^30 workgroups in one launch return 0 with a message on stderr; the call
+ * never aborts.
+ *
+ * work_bytes: the device memory one call holds for `count` pairs of n rows
+ * with every column and output in host memory (0 on a failure; needs a
+ * device).  last_timings: 4 values, milliseconds (stream events) of the last
+ * call's phases: sort, search, ranks, write. */
+typedef struct {
+  const void* input;
+  const void* table;
+} tachyon_mi355x_lookup_pair;
+TACHYON_C_EXPORT int tachyon_mi355x_lookup_permute_pairs(int field, size_t n, size_t usable_rows,
+                                                         const tachyon_mi355x_lookup_pair* pairs, size_t count,
+                                                         const void* blinds, void* const* out_input,
+                                                         void* const* out_table, uint64_t* out_misses);
+TACHYON_C_EXPORT size_t tachyon_mi355x_lookup_permute_work_bytes(size_t n, size_t count);
+TACHYON_C_EXPORT void tachyon_mi355x_lookup_permute_last_timings(float* out_ms);
+
 /* PLONK quotient: the vanishing argument's h(X) (zk/plonk/vanishing/
  * circuit_polynomial_builder.h:199-245, the Scroll shape; vanishing_utils.h:
  * 65-112, 167-196; vanishing_prover_impl.h:106-112) on device-resident

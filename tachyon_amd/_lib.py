@@ -242,6 +242,11 @@ SIGNATURES = [
     ("tachyon_mi355x_log_lookup_tile_rows", sz, []),
     ("tachyon_mi355x_log_lookup_work_bytes", sz, [sz, sz, sz]),
     ("tachyon_mi355x_log_lookup_last_timings", None, [fp]),
+    # Halo2 lookup: the permuted columns A' and S'
+    ("tachyon_mi355x_lookup_permute_pairs", i32, [i32, sz, sz, vp, sz, vp, ctypes.POINTER(ctypes.c_void_p),
+                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)]),
+    ("tachyon_mi355x_lookup_permute_work_bytes", sz, [sz, sz]),
+    ("tachyon_mi355x_lookup_permute_last_timings", None, [fp]),
     # field-generic NTT domains
     ("tachyon_mi355x_ntt_domain_create", vp, [i32, sz]),
     ("tachyon_mi355x_ntt_domain_destroy", None, [vp]),

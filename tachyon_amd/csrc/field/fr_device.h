@@ -1,5 +1,6 @@
-// Device helpers for the 8-limb scalar fields: 16-byte element access, wave
-// shuffles and the workgroup's product and sum scans.
+// Device helpers for the 8-limb scalar fields: 16-byte element access, the
+// order of canonical keys, wave shuffles and the workgroup's product and sum
+// scans.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,23 @@ template <class Fr>
 __device__ __forceinline__ void store_fr(Fr* p, const Fr& x) {
   reinterpret_cast<uint4*>(p)[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
   reinterpret_cast<uint4*>(p)[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+}
+
+// The order of the canonical integers *key and x: -1, 0, 1 for key <, =, > x;
+// most significant limb first, the low half read only behind an equal high one
+template <class Fr>
+__device__ __forceinline__ int compare_key(const Fr* key, const Fr& x) {
+  const uint4 hi = reinterpret_cast<const uint4*>(key)[1];
+  const uint32_t h[4] = {hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+  for (int i = 3; i >= 0; --i)
+    if (h[i] != x.v[4 + i]) return h[i] < x.v[4 + i] ? -1 : 1;
+  const uint4 lo = reinterpret_cast<const uint4*>(key)[0];
+  const uint32_t l[4] = {lo.x, lo.y, lo.z, lo.w};
+#pragma unroll
+  for (int i = 3; i >= 0; --i)
+    if (l[i] != x.v[i]) return l[i] < x.v[i] ? -1 : 1;
+  return 0;
 }
 
 // x of lane src (mod 64)

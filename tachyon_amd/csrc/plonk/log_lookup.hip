@@ -30,23 +30,6 @@ struct DevSumJob {
   uint32_t begin, end;  // its inputs in the call's pointer list
 };
 
-// The order of the canonical integers *key and x: -1, 0, 1 for key <, =, > x;
-// most significant limb first, the low half read only behind an equal high one
-template <class Fr>
-__device__ __forceinline__ int compare_key(const Fr* key, const Fr& x) {
-  const uint4 hi = reinterpret_cast<const uint4*>(key)[1];
-  const uint32_t h[4] = {hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-  for (int i = 3; i >= 0; --i)
-    if (h[i] != x.v[4 + i]) return h[i] < x.v[4 + i] ? -1 : 1;
-  const uint4 lo = reinterpret_cast<const uint4*>(key)[0];
-  const uint32_t l[4] = {lo.x, lo.y, lo.z, lo.w};
-#pragma unroll
-  for (int i = 3; i >= 0; --i)
-    if (l[i] != x.v[i]) return l[i] < x.v[i] ? -1 : 1;
-  return 0;
-}
-
 // Search and count.  grid: blocks_per_job x jobs, flat; a job is one input
 // column of one lookup, a thread one of its rows j < u.  BinarySearchByKey
 // over the lookup's sorted keys; a hit adds 1 to the counter of the hit
